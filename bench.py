@@ -13,8 +13,11 @@ Started without WORLD_SIZE (plain `python bench.py --gpus N`), this process only
 anything touches a GPU -- and relays rank 0's line; under torch.distributed.run it is one of the ranks.
 
 One JSON line is printed by rank 0.  `value` is whole-job cell-updates/s with all inputs resident in
-HBM when the timed region starts.  `roofline` is for the dominant kernel (measured live with HIP
-events on the library's stream); `cpu_baseline` is the CPU restatement timed on this host (rank 0, N = 1).
+HBM when the timed region starts; `ms_per_step` is the time of one of the --steps timed steps.  `roofline` is for the dominant
+kernel (measured live with HIP events on the library's stream); `cpu_baseline` is the CPU restatement timed on this host (rank 0, N = 1).
+
+--dump-outputs DIR writes the model state the last timed step left (prognostic fields, interiors) as DIR/<name>.npy, float64;
+the inputs and the number of steps before them depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -47,6 +50,24 @@ def alg_bytes_per_cell_update(args):
 
 B_ALG_PHASE = {"tendencies": 48.0, "step": 96.0, "rhs": 32.0, "fft_forward": 48.0, "spectral_solve": 16.0,
                "fft_backward": 48.0, "pcorrect": 56.0, "fused_tendency_step": 96.0, "poisson_fused": 80.0}
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: all files of all ranks together stay under this
+
+
+def dump_outputs(outdir, fields, rank, world):
+    """--dump-outputs: `fields` (name -> array) as <outdir>/<name>.npy in float64 (<name>_rank<r>.npy when N > 1).  When the
+    arrays do not fit in DUMP_BYTES, each one is replaced by a fixed sample of its entries: sorted flat indices (Fortran
+    order) drawn without replacement by PCG64 seed 0, the same for every run with the same arguments."""
+    os.makedirs(outdir, exist_ok=True)
+    fields = {k: np.asarray(v, dtype=np.float64) for k, v in fields.items()}
+    budget = DUMP_BYTES // world - 4096 * len(fields)                               # bytes of this rank; 4 kB per file for its header
+    fits = sum(a.size for a in fields.values()) * 8 <= budget
+    per_field = budget // len(fields) // 8                                          # entries
+    for name, a in fields.items():
+        if not fits and a.size > per_field:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per_field, replace=False))
+            a = a.ravel(order="F")[idx]
+        np.save(os.path.join(outdir, (f"{name}_rank{rank}" if world > 1 else name) + ".npy"), a)
 
 
 def cpu_baseline():
@@ -261,6 +282,11 @@ def run_config5(args, ocn, ctx, dist, rank, world, transport, real_stdout):
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t[0])
+    if args.dump_outputs:
+        fields = {"u": st.u.interior(), "v": st.v.interior(), "w": st.w.interior()}
+        fields.update({n: f.interior() for n, f in st.tracers.items()})
+        fields["eta"] = st.free_surface.eta.interior()
+        dump_outputs(args.dump_outputs, fields, rank, world)
     ms = el / args.steps * 1e3
     cells = Nx * Ny * Nz
     value = cells / (ms * 1e-3)
@@ -349,7 +375,12 @@ def main():
                     help="config 2 initial velocities: U[-0.5,0.5) per cell (SURVEY 8d, the metric) or a smooth sign-coherent field")
     ap.add_argument("--rehearse-hostemu", action="store_true",
                     help="plumbing rehearsal on the host emulation of the kernels (CPU only, tiny grid): NOT a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields the last timed step left as DIR/<name>.npy (float64, at most 64 MB in all: a fixed sample "
+                         "of each field when they are larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)           # never returns
@@ -453,7 +484,8 @@ def main():
     PH_ALL = list(B_ALG_PHASE) + ["fused_tracer_step", "fill_halos", "store", "copy_pressure", "time_step", "halo_exchange",
                                   "transpose", "amd_diffusivities", "hydrostatic"]
     # The card needs ~40 ms of load to leave its idle clocks (a 5-step run of config 2 measures 1.52 ms/step, a 200-step
-    # run 1.32): untimed spin-up steps run until 80 ms of stepping have passed (none if the warm-up already covers that).
+    # run 1.32): untimed spin-up steps come first.  On one GPU their number follows from the grid alone, never from a clock,
+    # so that the same arguments always time the same steps (--dump-outputs): 2^30 cell-updates, 64 steps or ~80 ms at 256^3.
     spinup = 0
     if args.rehearse_hostemu:
         pass
@@ -462,11 +494,10 @@ def main():
             ocn.time_step(model, dt)
         spinup = 40
     else:
-        t_spin = time.perf_counter()
-        while time.perf_counter() - t_spin < 0.08:
+        spinup = min(1024, max(16, (1 << 30) // (Nglobal[0] * Nglobal[1] * Nglobal[2])))
+        for _ in range(spinup):
             ocn.time_step(model, dt)
             ctx.sync()
-            spinup += 1
     nprobe = min(2, args.warmup)
     for _ in range(args.warmup - nprobe):
         ocn.time_step(model, dt)
@@ -510,6 +541,8 @@ def main():
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t[0])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: f.interior() for k, f in model.prognostic().items()}, rank, world)
 
     div = model.max_abs_divergence()
     cells = Nglobal[0] * Nglobal[1] * Nglobal[2]
