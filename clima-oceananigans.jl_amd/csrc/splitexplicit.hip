@@ -785,8 +785,9 @@ __global__ void k_hy_ab2_store(double* f, const double* gn, double* gm, double d
 //   Advection/tracer_advection_operators.jl:33-37, centered_advective_fluxes.jl:31-33   flux-form CenteredSecondOrder
 // One thread per cell; every operator keeps the reference's operand order, without contraction (see OCN_NO_CONTRACT).
 struct HyPhys {
-  int madv;          // 0 none, 1 VectorInvariant enstrophy-conserving, 2 energy-conserving, 3 WENO5(vector_invariant = VorticityStencil())
-  int xb, yb, jrow0, gNy;   // madv 3: Bounded x / y (boundary buffer), global row of the band's first row and global row count
+  int madv;          // 0 none, 1 VectorInvariant enstrophy-conserving, 2 energy-conserving, 3 WENO5(vector_invariant = VorticityStencil()),
+                     // 4 WENO5(vector_invariant = VelocityStencil())
+  int xb, yb, jrow0, gNy;   // madv 3, 4: Bounded x / y (boundary buffer), global row of the band's first row and global row count
   int cor;           // 0 none, 1 HydrostaticSphericalCoriolis enstrophy-conserving, 2 energy-conserving, 3 FPlane
   int tadv;          // 0 none, 1 CenteredSecondOrder, 2 CenteredFourthOrder, 3 UpwindBiasedFifthOrder, 4 WENO5 (Z weights)
   double f0;
@@ -798,7 +799,11 @@ struct HyMetric {
   int Nx, Ny, Nz, Hx, Hy, Hz;
 };
 
-__global__ void __launch_bounds__(256) k_hy_Guv(HyMetric g, HyPhys ph, const double* __restrict__ u, const double* __restrict__ v,
+// VS: madv 4 only, WENO5(vector_invariant = VelocityStencil()) -- its own instantiation, so that its wider stencil state does not
+// enter the register allocation of the other flavours (k_hy_Guv<false>: madv 0..3, the same code as without the bound).  Left to
+// itself the compiler gives k_hy_Guv<true> 99 VGPRs (4 waves per SIMD); asked for 5 it fits in 83 without spilling (6: 8 spilled)
+template <bool VS>
+__global__ void __launch_bounds__(256, VS ? 5 : 1) k_hy_Guv(HyMetric g, HyPhys ph, const double* __restrict__ u, const double* __restrict__ v,
                                                 const double* __restrict__ w, const double* __restrict__ p, double* __restrict__ Gu,
                                                 double* __restrict__ Gv, long syu, long szu, long syv, long szv, long syc, long szc) {
   OCN_NO_CONTRACT
@@ -844,34 +849,47 @@ __global__ void __launch_bounds__(256) k_hy_Guv(HyMetric g, HyPhys ph, const dou
   double Au = 0.0, Av = 0.0;
   if (ph.madv) {
     double vvU, vvV;
-    if (ph.madv == 1) {
+    if (!VS && ph.madv == 1) {
       const double z00 = zeta(0, 0);
       vvU = hy_div(-(0.5 * (z00 + zeta(0, 1))) * (0.5 * (Iy_dxv(-1) + Iy_dxv(0))), dxfc, rdxfc);
       vvV = hy_div(+(0.5 * (z00 + zeta(1, 0))) * (0.5 * (Ix_dyu(-1) + Ix_dyu(0))), dycf, rdycf);
-    } else if (ph.madv == 2) {
+    } else if (!VS && ph.madv == 2) {
       const double z00 = zeta(0, 0);
       vvU = hy_div(-(0.5 * (z00 * Ix_dxv(0) + zeta(0, 1) * Ix_dxv(1))), dxfc, rdxfc);
       vvV = hy_div(+(0.5 * (z00 * Iy_dyu(0) + zeta(1, 0) * Iy_dyu(1))), dycf, rdycf);
     } else {
       // WENO5(vector_invariant = VorticityStencil()) (vector_invariant_advection.jl:54-66): transporting velocity times the upwind-biased
       // WENO5 interpolation of zeta to the velocity point (stencils.h recon5: parity with the oracle to round-off, like the WENO tracer
-      // kernel), second order inside the boundary buffer of a Bounded direction (topologically_conditional_interpolation.jl:49-62)
+      // kernel), second order inside the boundary buffer of a Bounded direction (topologically_conditional_interpolation.jl:49-62).
+      // VelocityStencil() (VS): the same candidates of zeta, the smoothness indicators averaged over the grid-less interpolations
+      // I_y^f u and I_x^f v (Operators/interpolation_operators.jl:11) at zeta's points (weno_fifth_order.jl:285-293,405-436; stencils.h
+      // recon5_vs); they read the rows and columns zeta(0, -2) .. zeta(0, 3) and zeta(-2, 0) .. zeta(3, 0) read, so the halo stays 3
+      auto Uff = [&](int di, int dj) { return 0.5 * (U(di, dj - 1, 0) + U(di, dj, 0)); };
+      auto Vff = [&](int di, int dj) { return 0.5 * (V(di - 1, dj, 0) + V(di, dj, 0)); };
       const double vhat = hy_div(0.5 * (Iy_dxv(-1) + Iy_dxv(0)), dxfc, rdxfc), uhat = hy_div(0.5 * (Ix_dyu(-1) + Ix_dyu(0)), dycf, rdycf);
       const int jg = ph.jrow0 + j + 1, ig = i + 1;                  // 1-based global indices of the buffer test
       {
         const bool pos = vhat > 0.0;
         double zi;
         if (ph.yb && !(pos ? outside_left(jg, ph.gNy, 2) : outside_right(jg, ph.gNy, 2))) zi = 0.5 * (zeta(0, 0) + zeta(0, 1));
-        else zi = pos ? recon5<ADV_WENO_Z>(zeta(0, -2), zeta(0, -1), zeta(0, 0), zeta(0, 1), zeta(0, 2), true)
-                      : recon5<ADV_WENO_Z>(zeta(0, 3), zeta(0, 2), zeta(0, 1), zeta(0, 0), zeta(0, -1), false);
+        else if (!VS) zi = pos ? recon5<ADV_WENO_Z>(zeta(0, -2), zeta(0, -1), zeta(0, 0), zeta(0, 1), zeta(0, 2), true)
+                               : recon5<ADV_WENO_Z>(zeta(0, 3), zeta(0, 2), zeta(0, 1), zeta(0, 0), zeta(0, -1), false);
+        else zi = pos ? recon5_vs(zeta(0, -2), zeta(0, -1), zeta(0, 0), zeta(0, 1), zeta(0, 2), Uff(0, -2), Uff(0, -1), Uff(0, 0), Uff(0, 1),
+                                  Uff(0, 2), Vff(0, -2), Vff(0, -1), Vff(0, 0), Vff(0, 1), Vff(0, 2), true)
+                      : recon5_vs(zeta(0, 3), zeta(0, 2), zeta(0, 1), zeta(0, 0), zeta(0, -1), Uff(0, 3), Uff(0, 2), Uff(0, 1), Uff(0, 0),
+                                  Uff(0, -1), Vff(0, 3), Vff(0, 2), Vff(0, 1), Vff(0, 0), Vff(0, -1), false);
         vvU = -(vhat * zi);
       }
       {
         const bool pos = uhat > 0.0;
         double zi;
         if (ph.xb && !(pos ? outside_left(ig, g.Nx, 2) : outside_right(ig, g.Nx, 2))) zi = 0.5 * (zeta(0, 0) + zeta(1, 0));
-        else zi = pos ? recon5<ADV_WENO_Z>(zeta(-2, 0), zeta(-1, 0), zeta(0, 0), zeta(1, 0), zeta(2, 0), true)
-                      : recon5<ADV_WENO_Z>(zeta(3, 0), zeta(2, 0), zeta(1, 0), zeta(0, 0), zeta(-1, 0), false);
+        else if (!VS) zi = pos ? recon5<ADV_WENO_Z>(zeta(-2, 0), zeta(-1, 0), zeta(0, 0), zeta(1, 0), zeta(2, 0), true)
+                               : recon5<ADV_WENO_Z>(zeta(3, 0), zeta(2, 0), zeta(1, 0), zeta(0, 0), zeta(-1, 0), false);
+        else zi = pos ? recon5_vs(zeta(-2, 0), zeta(-1, 0), zeta(0, 0), zeta(1, 0), zeta(2, 0), Uff(-2, 0), Uff(-1, 0), Uff(0, 0), Uff(1, 0),
+                                  Uff(2, 0), Vff(-2, 0), Vff(-1, 0), Vff(0, 0), Vff(1, 0), Vff(2, 0), true)
+                      : recon5_vs(zeta(3, 0), zeta(2, 0), zeta(1, 0), zeta(0, 0), zeta(-1, 0), Uff(3, 0), Uff(2, 0), Uff(1, 0), Uff(0, 0),
+                                  Uff(-1, 0), Vff(3, 0), Vff(2, 0), Vff(1, 0), Vff(0, 0), Vff(-1, 0), false);
         vvV = +(uhat * zi);
       }
     }
@@ -1350,9 +1368,13 @@ static void hydro_tendencies(ocn_hydro* h) {
   ph.yb = g->topo[1] != OCN_PERIODIC;
   ph.jrow0 = g->j0;
   ph.gNy = g->gNy;
-  ocn_launch(k_hy_Guv, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d, (const double*)v->d, (const double*)h->w->d, (const double*)p->d,
-             h->gn[0]->d, h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0],
-             (long)p->T[0] * p->T[1]);
+#define HY_GUV(VS)                                                                                                                         \
+  ocn_launch(k_hy_Guv<VS>, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d,         \
+             (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (long)u->T[0],                     \
+             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1])
+  if (ph.madv == 4) HY_GUV(true);
+  else HY_GUV(false);
+#undef HY_GUV
   for (size_t q = 0; q < h->c.size(); q += 2) {
     const bool two = q + 1 < h->c.size();
     const double *c0 = h->c[q]->d, *c1 = two ? h->c[q + 1]->d : nullptr;
@@ -2161,8 +2183,8 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
   if (!h) return OCN_EINVAL;
   ocn_hgrid* g = h->lg;
   ocn_ctx* ctx = g->ctx;
-  if (momentum_advection < 0 || momentum_advection > 3 || coriolis < 0 || coriolis > 3 || tracer_advection < 0 || tracer_advection > 4) {
-    ocn_set_error(ctx, "ocn_hydro_set_physics: momentum_advection 0..3, coriolis 0..3, tracer_advection 0..4");
+  if (momentum_advection < 0 || momentum_advection > 4 || coriolis < 0 || coriolis > 3 || tracer_advection < 0 || tracer_advection > 4) {
+    ocn_set_error(ctx, "ocn_hydro_set_physics: momentum_advection 0..4, coriolis 0..3, tracer_advection 0..4");
     return OCN_EINVAL;
   }
   if ((coriolis == 1 || coriolis == 2) && g->kind != HG_LATLON) {
@@ -2170,7 +2192,7 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
     return OCN_EINVAL;
   }
   {
-    const int need = (tracer_advection >= 3 || momentum_advection == 3) ? 3 : tracer_advection == 2 ? 2 : 1;      // halo the schemes read
+    const int need = (tracer_advection >= 3 || momentum_advection >= 3) ? 3 : tracer_advection == 2 ? 2 : 1;      // halo the schemes read
     if (g->H[0] < need || g->H[1] < need || g->H[2] < need || (g->topo[0] == OCN_PERIODIC && g->N[0] < need)) {
       ocn_set_error(ctx, "ocn_hydro_set_physics: the stencils of this configuration read %d halo cell(s) in every direction", need);
       return OCN_EINVAL;

@@ -1,7 +1,7 @@
 // stencils.h -- device-side staggered-grid stencils shared by every kernel.
 //
 // Restated from the reference (paths relative to /root/reference/src):
-//   Advection/weno_fifth_order.jl:12-19,266-272,311-317,380-403,518-524   (WENO5, Z and JS weights)
+//   Advection/weno_fifth_order.jl:12-19,266-272,285-293,311-317,380-436,518-524   (WENO5, Z and JS weights; VelocityStencil)
 //   Advection/upwind_biased_fifth_order.jl:24-46                           (U5)
 //   Advection/centered_fourth_order.jl:17-33                               (4th-order symmetric)
 //   Advection/upwind_biased_advective_fluxes.jl:10                         (upwind_biased_product)
@@ -130,6 +130,48 @@ OCN_DEVFN double recon5(double A3, double A2, double A1, double A0, double B1, b
     const double den = fma(3.0, a0, fma(6.0, a1, a2));
     return fma(num, fast_rcp(den), A1);
   }
+}
+
+// ---- WENO5(vector_invariant = VelocityStencil()): zeta's candidates, smoothness from two tangential velocity stencils ----------
+// 12/13 beta_k + e of one five-point stencil, in recon5's difference form (same mirrored inputs, same as-written right-biased u_0, u_2)
+OCN_DEVFN void weno5_d(double A3, double A2, double A1, double A0, double B1, bool pos, double e, double& d0, double& d1, double& d2) {
+  const double e1 = A2 - A3, e2 = A1 - A2, e3 = A0 - A1, e4 = B1 - A0;
+  const double t0 = e4 - e3, t1 = e3 - e2, t2 = e2 - e1;
+  const double s2 = pos ? 2.0 : -2.0;
+  const double u0 = fma(-s2, pos ? e3 : e4, t0);
+  const double u1 = e2 + e3;
+  const double u2 = fma(s2, pos ? e2 : e1, t2);
+  const double c3 = 3.0 / 13.0;
+  d0 = fma(t0, t0, fma(u0 * c3, u0, e));
+  d1 = fma(t1, t1, fma(u1 * c3, u1, e));
+  d2 = fma(t2, t2, fma(u2 * c3, u2, e));
+}
+
+// The VelocityStencil member of left/right_biased_weno5_weights (weno_fifth_order.jl:405-436): the candidate polynomials of
+// (A3, A2, A1, A0, B1) -- zeta, mirrored as for recon5 -- weighted by Z weights whose smoothness indicators are
+// beta_k = (beta^u_k + beta^v_k) / 2 of the two tangential stencils (U3..UB1) and (V3..VB1), taken at zeta's index set and mirrored
+// alike (tangential_*_stencil_u/v, :285-293).  Only ratios of the (beta_k + eps) enter the weights, so d_k = 24/13 (beta_k + eps) =
+// (12/13 beta^u_k + 24/13 eps) + 12/13 beta^v_k: two d-triples and one add per k in place of recon5's one triple.
+OCN_DEVFN double recon5_vs(double A3, double A2, double A1, double A0, double B1, double U3, double U2, double U1, double U0, double UB1,
+                           double V3, double V2, double V1, double V0, double VB1, bool pos) {
+  double d0, d1, d2, dv0, dv1, dv2;
+  weno5_d(U3, U2, U1, U0, UB1, pos, 1e-6 * (24.0 / 13.0), d0, d1, d2);
+  weno5_d(V3, V2, V1, V0, VB1, pos, 0.0, dv0, dv1, dv2);
+  d0 += dv0;
+  d1 += dv1;
+  d2 += dv2;
+  const double e1 = A2 - A3, e2 = A1 - A2, e3 = A0 - A1, e4 = B1 - A0;
+  const double x3 = e3 + e3;
+  const double r0 = fma(-0.5, e4, x3);
+  const double r1 = x3 + e2;
+  const double r2 = fma(5.0 / 6.0, e2, (-1.0 / 3.0) * e1);
+  const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2;
+  const double P0 = q1 * q2, P1 = q0 * q2, P2 = q0 * q1;
+  const double tau = d2 - d0, tt = tau * tau, Q = q0 * P0;
+  const double a0 = fma(tt, P0, Q), a1 = fma(tt, P1, Q), a2 = fma(tt, P2, Q);
+  const double num = fma(a0, r0, fma(a1, r1, a2 * r2));
+  const double den = fma(3.0, a0, fma(6.0, a1, a2));
+  return fma(num, fast_rcp(den), A1);
 }
 
 // upwind reconstruction from memory: face between p[-s] and p[0], advecting velocity ut

@@ -364,6 +364,9 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
  * momentum_advection: 0 nothing, 1 VectorInvariant(scheme = EnstrophyConservingScheme()) -- the default --, 2 EnergyConservingScheme
  *   (Advection/vector_invariant_advection.jl:25-80), 3 WENO5(vector_invariant = VorticityStencil()): the vertical-vorticity term as
  *   transporting velocity times the upwind-biased WENO5 interpolation of zeta (vector_invariant_advection.jl:54-66), halo 3;
+ *   4 WENO5(vector_invariant = VelocityStencil()): the same term with the WENO5 weights taken from the averaged smoothness indicators
+ *   of the tangential velocities (I_y^f u, I_x^f v) instead of zeta's own (Advection/weno_fifth_order.jl:285-293,405-436), halo 3;
+ *   3 and 4 use uniform coefficients and Z weights, and the second-order boundary buffer of a Bounded direction;
  * coriolis: 0 nothing, 1 / 2 HydrostaticSphericalCoriolis(rotation_rate = coriolis_parameter) with the Enstrophy- / Energy-
  *   ConservingScheme (Coriolis/hydrostatic_spherical_coriolis.jl:29-66; LatitudeLongitudeGrid only), 3 FPlane(f = coriolis_parameter);
  * tracer_advection: 0 nothing, 1 CenteredSecondOrder() -- the default; bit-exact against the oracle --, 2 CenteredFourthOrder(),
