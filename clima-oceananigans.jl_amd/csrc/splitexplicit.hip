@@ -16,6 +16,8 @@
 //   .../calculate_hydrostatic_free_surface_tendencies.jl, hydrostatic_free_surface_tendency_kernel_functions.jl,
 //   Advection/vector_invariant_advection.jl, Coriolis/hydrostatic_spherical_coriolis.jl, Advection/tracer_advection_operators.jl
 //                                                                                                 k_hy_Guv, k_hy_Gc, k_hy_Gc_hi
+//   TurbulenceClosures/.../scalar_diffusivity.jl:101, scalar_biharmonic_diffusivity.jl:21 (horizontal closures)   hyclosure.h: k_hy_clo_uv,
+//                                                                                                 k_hy_clo_c
 //   .../hydrostatic_free_surface_ab2_step.jl:15-48, TimeSteppers/quasi_adams_bashforth_2.jl:70-166  ocn_hydro_ab2_step, k_hy_ab2, k_hy_momentum,
 //                                                                                                 k_hy_tracers, ocn_hydro_time_step
 //   .../compute_w_from_continuity.jl:31-36, NonhydrostaticModels/update_hydrostatic_pressure.jl:10-18,
@@ -777,7 +779,7 @@ __global__ void k_hy_ab2_store(double* f, const double* gn, double* gm, double d
   gm[c] = n;
 }
 
-// ---- third slice: calculate_tendencies! (no closure, no forcing, no immersed boundary) ----------------------------------------
+// ---- third slice: calculate_tendencies! (no forcing, no immersed boundary; the horizontal closures: hyclosure.h) -------------
 //   hydrostatic_free_surface_tendency_kernel_functions.jl:24-125   G_u, G_v, G_c
 //   Advection/vector_invariant_advection.jl:25-80                  VectorInvariant (enstrophy- / energy-conserving)
 //   Operators/vorticity_operators.jl:2-5                           zeta_3 at (Face, Face, Center)
@@ -1020,6 +1022,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
   }
 }
 
+// HorizontalScalarDiffusivity and HorizontalScalarBiharmonicDiffusivity: k_hy_clo_uv, k_hy_clo_c
+#include "hyclosure.h"
+
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
 // the level only, so the pivots beta_k and the multipliers t_k of the modified Thomas algorithm are tabulated once per (kappa, dt) on
@@ -1198,6 +1203,9 @@ struct ocn_hydro {
   std::vector<double> kap;
   struct ImpTab { double kappa, dt; double* d = nullptr; };      // device table of 4 Nz doubles: a, beta, 1 / beta, t
   std::vector<ImpTab> imptab;
+  // HorizontalScalarDiffusivity(nu2, kappa2) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4), explicit: entry 0 of kap2 / kap4 the
+  // viscosity, 1 + q the diffusivity of tracer q; empty or all zeros: off
+  std::vector<double> kap2, kap4;
 };
 
 static HyGrid hy_grid(const ocn_hgrid* g) {
@@ -1404,6 +1412,42 @@ static void hydro_tendencies(ocn_hydro* h) {
     else
       ocn_launch(k_hy_Gc<1>, grc, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1, G0, G1,
                  h->phys.tadv, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
+  }
+}
+
+// the explicit horizontal closures: G <- G - (Laplacian + biharmonic term) after the advection kernels (hyclosure.h); nothing is
+// launched for a field whose coefficients are all zero
+static void hydro_horizontal_closures(ocn_hydro* h) {
+  if (h->kap2.empty()) return;
+  const ocn_hgrid* g = h->lg;
+  const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
+  const HyClo m{g->topo[0] != OCN_PERIODIC, g->topo[1] != OCN_PERIODIC, g->j0, g->gNy};
+  const ocn_hfield *u = h->u, *v = h->v;
+  const double nu = h->kap2[0], nu4 = h->kap4[0];
+#define HY_CLO_UV(LAP, BIH)                                                                                                                \
+  ocn_launch(k_hy_clo_uv<LAP, BIH>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d, h->gn[0]->d, \
+             h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1])
+  if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(true, true);
+  else if (nu != 0.0) HY_CLO_UV(true, false);
+  else if (nu4 != 0.0) HY_CLO_UV(false, true);
+#undef HY_CLO_UV
+  for (size_t q = 0; q < h->c.size(); q += 2) {
+    const bool two = q + 1 < h->c.size();
+    const double k0 = h->kap2[1 + q], k1 = two ? h->kap2[2 + q] : 0.0, k40 = h->kap4[1 + q], k41 = two ? h->kap4[2 + q] : 0.0;
+    const bool lap = k0 != 0.0 || k1 != 0.0, bih = k40 != 0.0 || k41 != 0.0;
+    if (!lap && !bih) continue;
+    const ocn_hfield* c = h->c[q];
+    const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
+    double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
+#define HY_CLO_C(LAP, BIH)                                                                                                                 \
+  if (two)                                                                                                                                 \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 2>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
+               (long)c->T[0] * c->T[1]);                                                                                                   \
+  else                                                                                                                                     \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
+               (long)c->T[0] * c->T[1]);
+    if (lap && bih) { HY_CLO_C(true, true) } else if (lap) { HY_CLO_C(true, false) } else { HY_CLO_C(false, true) }
+#undef HY_CLO_C
   }
 }
 
@@ -2178,6 +2222,46 @@ int ocn_hydro_set_closure(ocn_hydro* h, double nu, int ntracers, const double* k
   return OCN_OK;
 }
 
+/* closure = HorizontalScalarDiffusivity(nu, kappa) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4), both explicit with constant
+ * coefficients, added to G^n of u, v and the tracers by ocn_hydro_calculate_tendencies / ocn_hydro_time_step; zeros switch a closure off */
+int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_t ntracers, const double* kappa, const double* kappa4) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  if (ntracers != (int)h->c.size() || (ntracers > 0 && (!kappa || !kappa4))) {
+    ocn_set_error(ctx, "ocn_hydro_set_horizontal_closure: %d diffusivities given, the model has %d tracers", (int)ntracers, (int)h->c.size());
+    return OCN_EINVAL;
+  }
+  bool lap = nu != 0.0, bih = nu4 != 0.0, ok = nu >= 0 && nu4 >= 0;
+  for (int q = 0; q < ntracers; ++q) {
+    ok = ok && kappa[q] >= 0 && kappa4[q] >= 0;
+    lap = lap || kappa[q] != 0.0;
+    bih = bih || kappa4[q] != 0.0;
+  }
+  if (!ok) {
+    ocn_set_error(ctx, "ocn_hydro_set_horizontal_closure: viscosities and diffusivities must be >= 0 (and not NaN)");
+    return OCN_EINVAL;
+  }
+  const int need = bih ? 2 : lap ? 1 : 0;      // required_halo_size: 1 (scalar_diffusivity.jl:104), 2 (scalar_biharmonic_diffusivity.jl:24)
+  if (g->H[0] < need || g->H[1] < need) {
+    ocn_set_error(ctx, "ocn_hydro_set_horizontal_closure: the %s closure reads %d halo cell(s) in x and y", bih ? "biharmonic" : "Laplacian", need);
+    return OCN_EINVAL;
+  }
+  h->kap2.assign(1 + (size_t)ntracers, 0.0);
+  h->kap4.assign(1 + (size_t)ntracers, 0.0);
+  h->kap2[0] = nu;
+  h->kap4[0] = nu4;
+  for (int q = 0; q < ntracers; ++q) {
+    h->kap2[1 + q] = kappa[q];
+    h->kap4[1 + q] = kappa4[q];
+  }
+  if (!lap && !bih) {
+    h->kap2.clear();
+    h->kap4.clear();
+  }
+  return OCN_OK;
+}
+
 /* ---- third slice: calculate_tendencies! and the whole time step ---------------------------------------------------------------- */
 int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, double coriolis_parameter, int tracer_advection) {
   if (!h) return OCN_EINVAL;
@@ -2218,6 +2302,7 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
   if (!h) return OCN_EINVAL;
   if (h->lg->H[0] < 1 || h->lg->H[1] < 1 || h->lg->H[2] < 1) return OCN_EINVAL;
   hydro_tendencies(h);
+  hydro_horizontal_closures(h);
   return api_done(h->fs->g->ctx, OCN_OK);
 }
 
@@ -2229,6 +2314,7 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
   if (euler)
     for (ocn_hfield* f : h->gm) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
   hydro_tendencies(h);
+  hydro_horizontal_closures(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
 }
 

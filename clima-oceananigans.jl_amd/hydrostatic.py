@@ -312,6 +312,54 @@ def update_hydrostatic_pressure(pHY, buoyancy, tracers):
     check(pHY.lib.ocn_hydro_pressure(pHY.h, kind, g, al, be, T.h if T else None, S.h if S else None), pHY.grid.ctx.h)
 
 
+class _ScalarClosure:
+    def __init__(self, nu=0.0, kappa=0.0):
+        self.nu = float(nu)
+        self.kappa = dict(kappa) if isinstance(kappa, dict) else float(kappa)
+
+    def kappa_of(self, name):
+        return float(self.kappa.get(name, 0.0)) if isinstance(self.kappa, dict) else self.kappa
+
+    def __repr__(self):
+        return f"{type(self).__name__}(nu={self.nu!r}, kappa={self.kappa!r})"
+
+
+class HorizontalScalarDiffusivity(_ScalarClosure):
+    """HorizontalScalarDiffusivity(nu, kappa): explicit horizontal Laplacian viscosity and diffusivity, constant coefficients
+    (TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl:101); kappa a number or {tracer: value}"""
+
+
+class HorizontalScalarBiharmonicDiffusivity(_ScalarClosure):
+    """HorizontalScalarBiharmonicDiffusivity(nu, kappa): explicit horizontal biharmonic viscosity and diffusivity [m^4/s], constant
+    coefficients (scalar_biharmonic_diffusivity.jl:21); needs 2 halo cells in x and y"""
+
+
+class VerticalScalarDiffusivity(_ScalarClosure):
+    """VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): the implicit vertical solve inside ab2_step!"""
+
+
+_CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity)
+
+
+def closure_parts(closure):
+    """None | (nu, kappa) | a closure object | a tuple of closure objects -> {kind: object}, at most one object of each kind"""
+    if closure is None:
+        return {}
+    if isinstance(closure, _CLOSURE_KINDS):
+        closure = (closure,)
+    elif isinstance(closure, tuple) and len(closure) == 2 and not any(isinstance(c, _CLOSURE_KINDS) for c in closure):
+        return {VerticalScalarDiffusivity: VerticalScalarDiffusivity(*closure)}     # the (nu, kappa) form of the implicit closure
+    parts = {}
+    for c in closure:
+        kind = type(c)
+        if kind not in _CLOSURE_KINDS:
+            raise ValueError(f"unsupported closure {c!r}: {', '.join(k.__name__ for k in _CLOSURE_KINDS)}")
+        if kind in parts:
+            raise ValueError(f"a closure tuple holds at most one {kind.__name__}")
+        parts[kind] = c
+    return parts
+
+
 class HydrostaticState:
     """the fields of a HydrostaticFreeSurfaceModel{SplitExplicitFreeSurface} the step after the tendencies touches: u, v, w, the
     tracers, G^n and G^- of the prognostic fields, pHY' and the free surface (hydrostatic_free_surface_model.jl:92-211)"""
@@ -352,12 +400,24 @@ class HydrostaticState:
         self.set_closure(closure)
 
     def set_closure(self, closure):
-        """None | (nu, kappa | {tracer: kappa}): VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa), constants"""
-        self.closure = closure
-        nu, kap = closure or (0.0, 0.0)
+        """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one
+        closure object | a tuple of them (at most one of each kind): HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
+        VerticalScalarDiffusivity; constant coefficients"""
+        parts = closure_parts(closure)
         names = list(self.tracers)
-        k = np.array([float(kap.get(n, 0.0)) if isinstance(kap, dict) else float(kap) for n in names] or [0.0])
-        check(self.lib.ocn_hydro_set_closure(self.h, float(nu), len(names), k.ctypes.data_as(C.POINTER(C.c_double))), self.grid.ctx.h)
+        PD = C.POINTER(C.c_double)
+        zero = _ScalarClosure()
+
+        def coeffs(kind):
+            c = parts.get(kind, zero)
+            return c.nu, np.array([c.kappa_of(n) for n in names] or [0.0])
+        nu2, k2 = coeffs(HorizontalScalarDiffusivity)
+        nu4, k4 = coeffs(HorizontalScalarBiharmonicDiffusivity)
+        check(self.lib.ocn_hydro_set_horizontal_closure(self.h, nu2, nu4, len(names), k2.ctypes.data_as(PD), k4.ctypes.data_as(PD)),
+              self.grid.ctx.h)
+        nu, k = coeffs(VerticalScalarDiffusivity)
+        check(self.lib.ocn_hydro_set_closure(self.h, nu, len(names), k.ctypes.data_as(PD)), self.grid.ctx.h)
+        self.closure = closure
 
     def set_physics(self, momentum_advection, coriolis, tracer_advection):
         """momentum_advection: None | "VectorInvariantEnstrophyConserving" | "VectorInvariantEnergyConserving" |

@@ -323,7 +323,8 @@ int ocn_sefs_step(ocn_sefs* s, const ocn_hfield* Gn_u, const ocn_hfield* Gn_v, c
  * time_step!(model::HydrostaticFreeSurfaceModel, dt) (TimeSteppers/quasi_adams_bashforth_2.jl:70-104) is
  *   calculate_tendencies!  ->  ab2_step!  ->  pressure_correct_velocities!  ->  store_tendencies!  ->  update_state!
  * The entry points below are everything after calculate_tendencies!; the caller (until the tendency kernels are in the
- * library too) fills G^n.  No closure / implicit vertical solve, no immersed boundary, flat bottom. */
+ * library too) fills G^n; the closures are those of ocn_hydro_set_closure / ocn_hydro_set_horizontal_closure below; no immersed boundary,
+ * flat bottom. */
 typedef struct ocn_hydro ocn_hydro;
 /* ab2_step_field! (quasi_adams_bashforth_2.jl:158-166): f += dt ((1.5 + chi) G^n - (0.5 + chi) G^-) over the grid's cells */
 int ocn_hfield_ab2_step(ocn_hfield* f, const ocn_hfield* Gn, const ocn_hfield* Gm, double dt, double chi);
@@ -360,7 +361,7 @@ int ocn_hydro_ab2_step(ocn_hydro* h, double dt, double chi);
  * 40 field sweeps) and leaves the same bits in every field, halos included. */
 int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused);
 
-/* ---- third slice: calculate_tendencies! (no closure, forcing or immersed boundary) and the whole time_step! ---------------
+/* ---- third slice: calculate_tendencies! (no forcing or immersed boundary; the closures below) and the whole time_step! ---------
  * momentum_advection: 0 nothing, 1 VectorInvariant(scheme = EnstrophyConservingScheme()) -- the default --, 2 EnergyConservingScheme
  *   (Advection/vector_invariant_advection.jl:25-80), 3 WENO5(vector_invariant = VorticityStencil()): the vertical-vorticity term as
  *   transporting velocity times the upwind-biased WENO5 interpolation of zeta (vector_invariant_advection.jl:54-66), halo 3;
@@ -380,6 +381,15 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
  * TurbulenceClosures/vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121); no flux through top
  * and bottom; ntracers must be the handle's; all zeros (the default) switch it off.  Other closures stay on the reference's path. */
 int ocn_hydro_set_closure(ocn_hydro* h, double nu, int32_t ntracers, const double* kappa);
+/* closure = HorizontalScalarDiffusivity(nu, kappa) (TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl:101;
+ * fluxes abstract_scalar_diffusivity_closure.jl:179-182,205-206) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4)
+ * (scalar_biharmonic_diffusivity.jl:21; fluxes and masks abstract_scalar_biharmonic_diffusivity_closure.jl:46-116), both explicit with
+ * constant coefficients, kappa / kappa4 per tracer: their flux divergences are subtracted from G^n of u, v and the tracers by
+ * ocn_hydro_calculate_tendencies and ocn_hydro_time_step, G <- G - (Laplacian term + biharmonic term), the reference's rounding for
+ * any tuple order of these two and the vertically implicit closure above.  They can be combined with ocn_hydro_set_closure.
+ * Zeros (the default) switch a closure off and launch nothing.  OCN_EINVAL for a negative or NaN coefficient, an ntracers that is
+ * not the handle's, a Laplacian coefficient with fewer than 1 halo cell in x or y, a biharmonic one with fewer than 2. */
+int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_t ntracers, const double* kappa, const double* kappa4);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
 int ocn_hydro_calculate_tendencies(ocn_hydro* h);
