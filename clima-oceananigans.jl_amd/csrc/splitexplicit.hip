@@ -18,6 +18,8 @@
 //                                                                                                 k_hy_Guv, k_hy_Gc, k_hy_Gc_hi
 //   TurbulenceClosures/.../scalar_diffusivity.jl:101, scalar_biharmonic_diffusivity.jl:21 (horizontal closures)   hyclosure.h: k_hy_clo_uv,
 //                                                                                                 k_hy_clo_c
+//   .../calculate_hydrostatic_free_surface_tendencies.jl:205-240, BoundaryConditions/apply_flux_bcs.jl:79-160 (flux boundary
+//   conditions)                                                                                   hyflux.h: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
 //   .../hydrostatic_free_surface_ab2_step.jl:15-48, TimeSteppers/quasi_adams_bashforth_2.jl:70-166  ocn_hydro_ab2_step, k_hy_ab2, k_hy_momentum,
 //                                                                                                 k_hy_tracers, ocn_hydro_time_step
 //   .../compute_w_from_continuity.jl:31-36, NonhydrostaticModels/update_hydrostatic_pressure.jl:10-18,
@@ -31,6 +33,8 @@
 // (k_se_multi), and replays the whole train from a hipGraph; every form leaves exactly the bits the launch-by-launch path leaves, halos
 // included (tests/test_reference_split_explicit.py).  The kernels of this file are compiled without contraction into FMAs and divide
 // through correctly rounded reciprocals (hy_div), so they also agree with the NumPy oracle bit for bit.
+#include <array>
+
 #include "internal.h"
 #include "stencils.h"
 
@@ -1025,6 +1029,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 // HorizontalScalarDiffusivity and HorizontalScalarBiharmonicDiffusivity: k_hy_clo_uv, k_hy_clo_c
 #include "hyclosure.h"
 
+// FluxBoundaryCondition on u, v and the tracers: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
+#include "hyflux.h"
+
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
 // the level only, so the pivots beta_k and the multipliers t_k of the modified Thomas algorithm are tabulated once per (kappa, dt) on
@@ -1206,6 +1213,10 @@ struct ocn_hydro {
   // HorizontalScalarDiffusivity(nu2, kappa2) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4), explicit: entry 0 of kap2 / kap4 the
   // viscosity, 1 + q the diffusivity of tracer q; empty or all zeros: off
   std::vector<double> kap2, kap4;
+  // FluxBoundaryCondition per field (0 u, 1 v, 2 + q tracer q) and side (OCN_WEST .. OCN_TOP); empty: none anywhere.  An array (kind 2)
+  // lives on the device and is kept for reuse when the condition is replaced
+  struct FluxBC { int kind = 0; double value = 0.0; double* d = nullptr; };
+  std::vector<std::array<FluxBC, 6>> fbc;
 };
 
 static HyGrid hy_grid(const ocn_hgrid* g) {
@@ -1448,6 +1459,44 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
                (long)c->T[0] * c->T[1]);
     if (lap && bih) { HY_CLO_C(true, true) } else if (lap) { HY_CLO_C(true, false) } else { HY_CLO_C(false, true) }
 #undef HY_CLO_C
+  }
+}
+
+// the flux boundary conditions (hyflux.h): after the interior terms, x sides, then y sides, then z sides, as the reference issues them;
+// nothing is launched for a direction without an active condition.  South / north conditions act on the band touching that wall only
+static void hydro_flux_bcs(ocn_hydro* h) {
+  if (h->fbc.empty()) return;
+  const ocn_hgrid* g = h->lg;
+  const HyMetric m = hy_metric(g);
+  const int Nx = g->N[0], Ny = g->N[1], Nz = g->N[2];
+  for (int dir = 0; dir < 3; ++dir) {
+    HyFluxTab t;
+    t.n = 0;
+    auto flush = [&]() {
+      if (!t.n) return;
+      if (dir == 0) ocn_launch(k_hy_flux_x, dim3((Ny + 63) / 64, Nz, 1), dim3(64, 1, 1), g->ctx->stream, m, t);
+      else if (dir == 1) ocn_launch(k_hy_flux_y, dim3((Nx + 63) / 64, Nz, 1), dim3(64, 1, 1), g->ctx->stream, m, t);
+      else ocn_launch(k_hy_flux_z, dim3((Nx + 63) / 64, (Ny + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, m, t);
+      t.n = 0;
+    };
+    for (size_t f = 0; f < h->fbc.size(); ++f)
+      for (int side = 2 * dir; side < 2 * dir + 2; ++side) {
+        const ocn_hydro::FluxBC& b = h->fbc[f][side];
+        if (!b.kind || (side == OCN_SOUTH && !g->wall_lo) || (side == OCN_NORTH && !g->wall_hi)) continue;
+        if (t.n == HY_FLUX_MAX) flush();
+        const ocn_hfield* fld = f == 0 ? h->u : f == 1 ? h->v : h->c[f - 2];
+        HyFluxBC& e = t.e[t.n++];
+        e.G = h->gn[f]->d;
+        e.f = fld->d;
+        e.a = b.d;
+        e.value = b.value;
+        e.sy = (long)fld->T[0];
+        e.sz = (long)fld->T[0] * fld->T[1];
+        e.kind = b.kind;
+        e.side = side;
+        e.loc = f == 0 ? 1 : f == 1 ? 2 : 0;
+      }
+    flush();
   }
 }
 
@@ -2106,6 +2155,8 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   hipFree(h->Vn);
   hipFree(h->frow);
   for (auto& e : h->imptab) hipFree(e.d);
+  for (auto& f : h->fbc)
+    for (auto& b : f) hipFree(b.d);
   delete h;
   hgrid_release(g);
 }
@@ -2262,6 +2313,51 @@ int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_
   return OCN_OK;
 }
 
+/* FluxBoundaryCondition on one side of u (field 0), v (field 1) or tracer q (field 2 + q), added to G^n after the interior terms
+ * (apply_flux_bcs.jl); kind 0 none, 1 constant, 2 array, 3 linear drag (z sides) */
+int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kind, double value, const double* host, int64_t n) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const int nf = 2 + (int)h->c.size();
+  if (field < 0 || field >= nf) {
+    ocn_set_error(ctx, "ocn_hydro_set_flux_bc: field %d out of range (0 u, 1 v, 2 .. %d the tracers)", (int)field, nf - 1);
+    return OCN_EINVAL;
+  }
+  if (side < OCN_WEST || side > OCN_TOP || kind < 0 || kind > 3) {
+    ocn_set_error(ctx, "ocn_hydro_set_flux_bc: side %d (0 .. 5) or kind %d (0 .. 3) out of range", (int)side, (int)kind);
+    return OCN_EINVAL;
+  }
+  const int d = side / 2;
+  const int64_t need = d == 2 ? (int64_t)g->N[0] * g->N[1] : d == 0 ? (int64_t)g->N[1] * g->N[2] : (int64_t)g->N[0] * g->N[2];
+  if (kind != 0) {
+    const char* why = nullptr;
+    if (d < 2 && g->topo[d] == OCN_PERIODIC) why = "a flux through a Periodic side";
+    else if ((field == 0 && d == 0) || (field == 1 && d == 1)) why = "a flux condition on the normal velocity's own wall (u west / east, v south / north)";
+    else if (kind == 3 && d != 2) why = "linear drag on an x or y side (z sides only)";
+    else if (kind == 3 && !(value >= 0)) why = "a linear drag rate must be >= 0";
+    else if (kind == 2 && (!host || n != need)) why = "a wrong number of values for this side";
+    if (why) {
+      ocn_set_error(ctx, "ocn_hydro_set_flux_bc: %s (field %d, side %d, kind %d, n %lld, expected %lld)", why, (int)field, (int)side, (int)kind,
+                    (long long)n, (long long)need);
+      return OCN_EINVAL;
+    }
+  }
+  if (h->fbc.empty()) {
+    if (kind == 0) return OCN_OK;
+    h->fbc.resize(nf);
+  }
+  ocn_hydro::FluxBC& b = h->fbc[field][side];
+  if (kind == 2) {
+    OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));        // a step already queued may still read the previous values
+    if (!b.d) OCN_HIP_CHECK(ctx, hipMalloc((void**)&b.d, need * sizeof(double)));
+    OCN_HIP_CHECK(ctx, hipMemcpy(b.d, host, need * sizeof(double), hipMemcpyHostToDevice));
+  }
+  b.kind = kind;
+  b.value = value;
+  return OCN_OK;
+}
+
 /* ---- third slice: calculate_tendencies! and the whole time step ---------------------------------------------------------------- */
 int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, double coriolis_parameter, int tracer_advection) {
   if (!h) return OCN_EINVAL;
@@ -2303,6 +2399,7 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
   if (h->lg->H[0] < 1 || h->lg->H[1] < 1 || h->lg->H[2] < 1) return OCN_EINVAL;
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
+  hydro_flux_bcs(h);
   return api_done(h->fs->g->ctx, OCN_OK);
 }
 
@@ -2315,6 +2412,7 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
     for (ocn_hfield* f : h->gm) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
+  hydro_flux_bcs(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
 }
 

@@ -360,13 +360,41 @@ def closure_parts(closure):
     return parts
 
 
+class FluxBoundaryCondition:
+    """FluxBoundaryCondition(condition) on one side of u, v or a tracer (BoundaryConditions/boundary_condition.jl:106-113).  condition:
+    a number; an array in getbc's index order over the WHOLE grid (z sides [i, j]: Nx x Ny, x sides [j, k]: Ny x Nz, y sides [i, k]:
+    Nx x Nz; a latitude band takes its own rows); or a callable of the side's two coordinates -- f(lambda, phi) / f(x, y) on z sides,
+    f(phi, z) / f(y, z) on x sides, f(lambda, z) / f(x, z) on y sides -- evaluated once at the boundary nodes of the field's location
+    (the time-independent continuous form)"""
+
+    def __init__(self, condition):
+        self.condition = condition
+
+    def __repr__(self):
+        return f"FluxBoundaryCondition({self.condition!r})"
+
+
+class LinearDrag:
+    """the discrete-form flux -rate * f[i, j, k_b] of the field f at its bottom (k_b = 1) or top (k_b = Nz) cell, rate >= 0: z sides only.
+    `- mu * u[i, j, 1]` of validation/barotropic_gyre is LinearDrag(mu), `- mu * Lz * u[i, j, 1]` of abernathey_channel LinearDrag(mu * Lz)"""
+
+    def __init__(self, rate):
+        self.rate = float(rate)
+
+    def __repr__(self):
+        return f"LinearDrag({self.rate!r})"
+
+
+SIDES = ("west", "east", "south", "north", "bottom", "top")     # OCN_WEST .. OCN_TOP
+
+
 class HydrostaticState:
     """the fields of a HydrostaticFreeSurfaceModel{SplitExplicitFreeSurface} the step after the tendencies touches: u, v, w, the
     tracers, G^n and G^- of the prognostic fields, pHY' and the free surface (hydrostatic_free_surface_model.jl:92-211)"""
 
     def __init__(self, grid, tracers=("T", "S"), buoyancy=None, substeps=20, gravitational_acceleration=g_Earth, free_surface=None,
                  momentum_advection="VectorInvariantEnstrophyConserving", coriolis=None, tracer_advection="CenteredSecondOrder",
-                 barotropic_overlap=0, closure=None):
+                 barotropic_overlap=0, closure=None, boundary_conditions=None):
         self.grid, self.lib = grid, grid.lib
         self.chi = 0.1
         self.u, self.v, self.w = Field3(grid, Face, Center), Field3(grid, Center, Face), Field3(grid, Center, Center, Face)
@@ -398,6 +426,65 @@ class HydrostaticState:
         check(self.lib.ocn_hydro_create(C.byref(d), C.byref(self.h)), grid.ctx.h)
         self.set_physics(momentum_advection, coriolis, tracer_advection)
         self.set_closure(closure)
+        self.set_boundary_conditions(boundary_conditions)
+
+    def _flux_args(self, name, side, bc):
+        """(kind, value, array) of ocn_hydro_set_flux_bc for the condition `bc` on `side` of field `name`; ValueError where the library
+        would refuse it"""
+        if bc is None:
+            return 0, 0.0, None
+        g = self.grid
+        d = SIDES.index(side) // 2
+        where = f"{bc!r} on the {side} of {name}"
+        if not isinstance(bc, (FluxBoundaryCondition, LinearDrag)):
+            raise ValueError(f"{where}: a boundary condition is a FluxBoundaryCondition or a LinearDrag")
+        if d < 2 and g.topology[d] == Periodic:
+            raise ValueError(f"{where}: that side is Periodic")
+        if (name, d) in (("u", 0), ("v", 1)):
+            raise ValueError(f"{where}: a flux through the normal velocity's own wall")
+        if isinstance(bc, LinearDrag):
+            if d != 2:
+                raise ValueError(f"{where}: linear drag is a bottom / top condition")
+            if not bc.rate >= 0:
+                raise ValueError(f"{where}: the drag rate must be >= 0")
+            return 3, bc.rate, None
+        cond = bc.condition
+        if isinstance(cond, (int, float, np.number)) and not isinstance(cond, bool):
+            return 1, float(cond), None
+        lx, ly = {"u": (Face, Center), "v": (Center, Face)}.get(name, (Center, Center))
+        shape = [(g.Ny, g.Nz), (g.Nx, g.Nz), (g.Nx, g.Ny)][d]
+        if callable(cond):
+            a, b = [(g.nodes(ly, 1)[:g.Ny], g.znodes(Center)), (g.nodes(lx, 0)[:g.Nx], g.znodes(Center)),
+                    (g.nodes(lx, 0)[:g.Nx], g.nodes(ly, 1)[:g.Ny])][d]
+            arr = np.broadcast_to(np.asarray(cond(a.reshape(-1, 1), b.reshape(1, -1)), dtype=np.float64), shape)
+        else:
+            arr = np.asarray(cond, dtype=np.float64)
+            whole = [(g.global_Ny, g.Nz), (g.Nx, g.Nz), (g.Nx, g.global_Ny)][d]
+            if arr.shape != whole:
+                raise ValueError(f"{where}: an array of shape {whole} expected, got {arr.shape}")
+            if d == 0:
+                arr = arr[g.j0:g.j0 + g.Ny]
+            elif d == 2:
+                arr = arr[:, g.j0:g.j0 + g.Ny]
+        return 2, 0.0, np.ascontiguousarray(arr.ravel(order="F"))
+
+    def set_boundary_conditions(self, boundary_conditions):
+        """None | {field: {side: FluxBoundaryCondition | LinearDrag}} with field "u", "v" or a tracer and side one of SIDES; replaces
+        every earlier condition: a field or side left out has none (ocn_hydro_set_flux_bc)"""
+        bcs = dict(boundary_conditions or {})
+        names = ["u", "v"] + list(self.tracers)
+        for n, sides in bcs.items():
+            if n not in names:
+                raise ValueError(f"boundary conditions for {n!r}: the model's fields are {names}")
+            bad = [s for s in sides if s not in SIDES]
+            if bad:
+                raise ValueError(f"unknown sides {bad} of {n}: {SIDES}")
+        plan = [(f, s, *self._flux_args(n, side, bcs.get(n, {}).get(side))) for f, n in enumerate(names) for s, side in enumerate(SIDES)]
+        PD = C.POINTER(C.c_double)
+        for f, s, kind, value, arr in plan:
+            check(self.lib.ocn_hydro_set_flux_bc(self.h, f, s, kind, value, None if arr is None else arr.ctypes.data_as(PD),
+                                                 0 if arr is None else arr.size), self.grid.ctx.h)
+        self.boundary_conditions = bcs
 
     def set_closure(self, closure):
         """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one

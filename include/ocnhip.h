@@ -361,7 +361,7 @@ int ocn_hydro_ab2_step(ocn_hydro* h, double dt, double chi);
  * 40 field sweeps) and leaves the same bits in every field, halos included. */
 int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused);
 
-/* ---- third slice: calculate_tendencies! (no forcing or immersed boundary; the closures below) and the whole time_step! ---------
+/* ---- third slice: calculate_tendencies! (no forcing or immersed boundary; the closures and flux conditions below) and time_step! ----
  * momentum_advection: 0 nothing, 1 VectorInvariant(scheme = EnstrophyConservingScheme()) -- the default --, 2 EnergyConservingScheme
  *   (Advection/vector_invariant_advection.jl:25-80), 3 WENO5(vector_invariant = VorticityStencil()): the vertical-vorticity term as
  *   transporting velocity times the upwind-biased WENO5 interpolation of zeta (vector_invariant_advection.jl:54-66), halo 3;
@@ -390,6 +390,19 @@ int ocn_hydro_set_closure(ocn_hydro* h, double nu, int32_t ntracers, const doubl
  * Zeros (the default) switch a closure off and launch nothing.  OCN_EINVAL for a negative or NaN coefficient, an ntracers that is
  * not the handle's, a Laplacian coefficient with fewer than 1 halo cell in x or y, a biharmonic one with fewer than 2. */
 int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_t ntracers, const double* kappa, const double* kappa4);
+/* FluxBoundaryCondition on one side (OCN_WEST .. OCN_TOP) of u (field 0), v (field 1) or tracer q (field 2 + q), applied to G^n after
+ * the interior tendencies by ocn_hydro_calculate_tendencies / ocn_hydro_time_step (apply_flux_bcs.jl).  kind 0: none (default);
+ * 1: the constant `value`; 2: `n` values at `host` (z sides Nx x Ny, x sides Ny x Nz, y sides Nx x Nz of this grid or band,
+ * first index fastest), copied to the device; 3: linear drag, flux = -value * field at the boundary cell (z sides only).
+ * West / south / bottom: G[1] += (flux A) / V; east / north / top: G[N] -= (flux A) / V, with the face area A and the cell volume V
+ * of the field's location.  On latitude bands a south / north condition acts on the band touching that wall only; x sides and z
+ * sides take the band's rows.  Fluxes on u and v reach the barotropic forcing through G^n; halo fills and the implicit vertical
+ * solve do not change.
+ * OCN_EINVAL: a Periodic side, the normal velocity's own wall (u west/east, v south/north), a wrong n, value < 0 for kind 3,
+ * a field index out of range.  Calling again replaces the condition; array storage is reused.  A kind-2 call synchronises the
+ * context's stream before it copies, so a step already queued reads the previous values: replacing the array between steps is
+ * time-varying forcing. */
+int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kind, double value, const double* host, int64_t n);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
 int ocn_hydro_calculate_tendencies(ocn_hydro* h);
