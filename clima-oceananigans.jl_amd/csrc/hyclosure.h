@@ -27,6 +27,22 @@ struct HyClo {
   int xb, yb, jrow0, gNy;   // Bounded x / y; global row of the band's first row; global row count
 };
 
+// the vertical flux divergence of a ConvectiveAdjustmentVerticalDiffusivity in the same pass (hyconvect.h), VZ of the kernels below:
+// 0 none (the instances without it), 1 the explicit form (-nu d_z u, -nu d_z v, -kappa d_z c), 2 the implicit form's interior-face
+// w-shear of u and v (-nu d_x w, -nu d_y w; the boundary faces keep the explicit flux).  A tuple sums its closures' terms in tuple
+// order: o[0..2] list the Laplacian (0), biharmonic (1) and convective-adjustment (2) terms in that order, absent terms are zero.
+struct HyCvTerm {
+  const double* K;         // nu (u, v) or kappa (tracers), (Center, Center, Face)
+  const double* w;         // VZ == 2
+  long syk, szk, syw, szw;
+  int o0, o1, o2;
+};
+__device__ inline double hy_cv_sum(const HyCvTerm& z, double l, double b, double v) {
+  OCN_NO_CONTRACT
+  auto pick = [&](int o) { return o == 0 ? l : o == 1 ? b : v; };
+  return (pick(z.o0) + pick(z.o1)) + pick(z.o2);
+}
+
 struct HyCloAt {
   // one cell: reference indices (I, J) of the thread's cell, 1-based, J global
   const HyMetric& g;
@@ -41,10 +57,10 @@ struct HyCloAt {
 };
 
 // G_u, G_v -= closure terms at the cell (i, j, k).  LAP: HorizontalScalarDiffusivity(nu); BIH: HorizontalScalarBiharmonicDiffusivity(nu4)
-template <bool LAP, bool BIH>
+template <bool LAP, bool BIH, int VZ = 0>
 __global__ void __launch_bounds__(256) k_hy_clo_uv(HyMetric g, HyClo m, double nu, double nu4, const double* __restrict__ u,
                                                    const double* __restrict__ v, double* __restrict__ Gu, double* __restrict__ Gv, long syu,
-                                                   long szu, long syv, long szv) {
+                                                   long szu, long syv, long szv, HyCvTerm z) {
   OCN_NO_CONTRACT
   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y, k = blockIdx.z;
   if (i >= g.Nx || j >= g.Ny) return;
@@ -54,7 +70,7 @@ __global__ void __launch_bounds__(256) k_hy_clo_uv(HyMetric g, HyClo m, double n
   auto V = [&](int di, int dj) { return v[cv + di + dj * syv]; };
   const double dz = g.dzc[k];
   const double rVfc = 1 / (g.azcc[r] * dz), rVcf = 1 / (g.azff[r] * dz);      // 1 / V^fcc (Az^fc = Az^cc), 1 / V^cfc (Az^cf = Az^ff)
-  double Tu = 0.0, Tv = 0.0;
+  double Tu = 0.0, Tv = 0.0, bu_ = 0.0, bv_ = 0.0;
   if (LAP) {
     // div_xy^ccc and zeta_3^ffc at (i + di, j + dj)
     auto delta = [&](int di, int dj) {
@@ -113,18 +129,45 @@ __global__ void __launch_bounds__(256) k_hy_clo_uv(HyMetric g, HyClo m, double n
     const double gx0 = (g.dycf[r] * dz) * (nu4 * zs00), gx1 = (g.dycf[r] * dz) * (nu4 * zs10);
     const double gy0 = (g.dxfc[r - 1] * dz) * (nu4 * ds0m), gy1 = (g.dxfc[r] * dz) * (nu4 * ds00);
     const double bv = rVcf * ((gx1 - gx0) + (gy1 - gy0));
-    Tu = LAP ? Tu + bu : bu;
-    Tv = LAP ? Tv + bv : bv;
+    if (VZ) {
+      bu_ = bu;
+      bv_ = bv;
+    } else {
+      Tu = LAP ? Tu + bu : bu;
+      Tv = LAP ? Tv + bv : bv;
+    }
+  }
+  if (VZ) {
+    // faces k + 1 (K) and k + 2 (K + 1) of this cell; nu at the velocity points 0.5 (nu[i-1] + nu[i]) / 0.5 (nu[j-1] + nu[j])
+    const int Nz = g.Nz;
+    const long ck = (i + g.Hx) + (long)r * z.syk + (long)(k + g.Hz) * z.szk;
+    const double azu = g.azcc[r], azv = g.azff[r];          // Az^fcf = Az^cc, Az^cff = Az^ff
+    auto flux = [&](int e, bool isv) {                       // the flux at face K + e
+      const long q = ck + (long)e * z.szk;
+      const double nf = isv ? 0.5 * (z.K[q - z.syk] + z.K[q]) : 0.5 * (z.K[q - 1] + z.K[q]);
+      const int K = k + 1 + e;
+      if (VZ == 2 && K > 1 && K < Nz + 1) {
+        const long cw = (i + g.Hx) + (long)r * z.syw + (long)(K - 1 + g.Hz) * z.szw;
+        return isv ? -nf * ((z.w[cw] - z.w[cw - z.syw]) / g.dycf[r]) : -nf * ((z.w[cw] - z.w[cw - 1]) / g.dxfc[r]);
+      }
+      const long c = (isv ? cv : cu) + (long)e * (isv ? szv : szu);
+      const double* f = isv ? v : u;
+      return -nf * ((f[c] - f[c - (isv ? szv : szu)]) / g.dzf[K - 1]);
+    };
+    const double zu = rVfc * (azu * flux(1, false) - azu * flux(0, false));
+    const double zv = rVcf * (azv * flux(1, true) - azv * flux(0, true));
+    Tu = hy_cv_sum(z, LAP ? Tu : 0.0, bu_, zu);
+    Tv = hy_cv_sum(z, LAP ? Tv : 0.0, bv_, zv);
   }
   Gu[cu] = Gu[cu] - Tu;
   Gv[cv] = Gv[cv] - Tv;
 }
 
 // G_c -= closure terms for NT tracers at the cell (i, j, k); kap[t] the Laplacian, kap4[t] the biharmonic diffusivity of tracer t
-template <bool LAP, bool BIH, int NT>
+template <bool LAP, bool BIH, int NT, int VZ = 0>
 __global__ void __launch_bounds__(256) k_hy_clo_c(HyMetric g, HyClo m, double kap0, double kap1, double kap40, double kap41,
                                                   const double* __restrict__ c0, const double* __restrict__ c1, double* __restrict__ G0,
-                                                  double* __restrict__ G1, long syc, long szc) {
+                                                  double* __restrict__ G1, long syc, long szc, HyCvTerm z) {
   OCN_NO_CONTRACT
   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y, k = blockIdx.z;
   if (i >= g.Nx || j >= g.Ny) return;
@@ -141,7 +184,7 @@ __global__ void __launch_bounds__(256) k_hy_clo_c(HyMetric g, HyClo m, double ka
     auto C = [&](int di, int dj) { return c[di + dj * syc]; };
     auto dxc = [&](int di, int dj) { const int q = r + dj; return hy_div(C(di, dj) - C(di - 1, dj), g.dxfc[q], g.r_dxfc[q]); };   // d_x^fcc c
     auto dyc = [&](int di, int dj) { const int q = r + dj; return hy_div(C(di, dj) - C(di, dj - 1), g.dycf[q], g.r_dycf[q]); };   // d_y^cfc c
-    double T = 0.0;
+    double T = 0.0, b_ = 0.0;
     if (LAP) {
       const double kap = t ? kap1 : kap0;
       // flux = -kappa d c
@@ -164,7 +207,15 @@ __global__ void __launch_bounds__(256) k_hy_clo_c(HyMetric g, HyClo m, double ka
       const double sy0 = my0 ? 0.0 : g.r_azff[r] * (g.dxfc[r] * l00 - g.dxfc[r - 1] * l0m);
       const double sy1 = my1 ? 0.0 : g.r_azff[r + 1] * (g.dxfc[r + 1] * l0p - g.dxfc[r] * l00);
       const double b = rV * ((ax * (kap4 * sx1) - ax * (kap4 * sx0)) + (ay1 * (kap4 * sy1) - ay0 * (kap4 * sy0)));
-      T = LAP ? T + b : b;
+      if (VZ) b_ = b;
+      else T = LAP ? T + b : b;
+    }
+    if (VZ) {
+      // -kappa d_z c at faces k + 1 and k + 2 of this cell (kappa as it is: one kappa serves every tracer)
+      const long ck = (i + g.Hx) + (long)r * z.syk + (long)(k + g.Hz) * z.szk;
+      auto flux = [&](int e) { return -z.K[ck + (long)e * z.szk] * ((c[(long)e * szc] - c[(long)(e - 1) * szc]) / g.dzf[k + e]); };
+      const double az = g.azcc[r];
+      T = hy_cv_sum(z, LAP ? T : 0.0, b_, rV * (az * flux(1) - az * flux(0)));
     }
     double* G = (t ? G1 : G0) + cc;
     *G = *G - T;

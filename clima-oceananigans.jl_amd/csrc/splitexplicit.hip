@@ -1032,6 +1032,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 // FluxBoundaryCondition on u, v and the tracers: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
 #include "hyflux.h"
 
+// ConvectiveAdjustmentVerticalDiffusivity: k_hy_cv_diff, k_hy_cv_implicit, k_hy_cv_momentum, k_hy_cv_ab2 (its explicit terms: hyclosure.h)
+#include "hyconvect.h"
+
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
 // the level only, so the pivots beta_k and the multipliers t_k of the modified Thomas algorithm are tabulated once per (kappa, dt) on
@@ -1217,6 +1220,16 @@ struct ocn_hydro {
   // lives on the device and is kept for reuse when the condition is replaced
   struct FluxBC { int kind = 0; double value = 0.0; double* d = nullptr; };
   std::vector<std::array<FluxBC, 6>> fbc;
+  // ConvectiveAdjustmentVerticalDiffusivity: on, discretization (0 vertically implicit, 1 explicit), coefficients, the order of the
+  // explicit terms in the tuple (0 Laplacian, 1 biharmonic, 2 this closure), its diffusivity fields and the solve's scratch
+  struct Cavd {
+    bool on = false;
+    int disc = 0;
+    double kc = 0.0, nuc = 0.0, kb = 0.0, nub = 0.0;
+    int order[3] = {0, 1, 2};
+    ocn_hfield *kap = nullptr, *nu = nullptr;
+    double* t = nullptr;
+  } cv;
 };
 
 static HyGrid hy_grid(const ocn_hgrid* g) {
@@ -1358,6 +1371,33 @@ static int hydro_allgather_rows(ocn_hydro* h) {
   }
   return comm_exchange(c, sends, recvs);
 }
+// calculate_diffusivities! of the ConvectiveAdjustmentVerticalDiffusivity, halos included (hyconvect.h)
+static void hydro_cv_diffusivities(ocn_hydro* h) {
+  const ocn_hgrid* g = h->lg;
+  ocn_hfield *K = h->cv.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  const bool yb = g->topo[1] != OCN_PERIODIC;
+  ocn_launch(k_hy_cv_diff, dim3((K->T[0] + 63) / 64, (K->T[1] + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, hy_grid(g), h->buoy, h->cv.kc, h->cv.nuc,
+             h->cv.kb, h->cv.nub, T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, K->d, h->cv.nu->d,
+             K->T[0], K->T[1], (int)(g->topo[0] != OCN_PERIODIC), (int)(yb && g->wall_lo), (int)(yb && g->wall_hi), (long)K->T[0],
+             (long)K->T[0] * K->T[1]);
+}
+// the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient
+static bool hydro_cv_implicit_uv(const ocn_hydro* h) { return h->cv.on && h->cv.disc == 0 && (h->cv.nuc != 0.0 || h->cv.nub != 0.0); }
+static bool hydro_cv_implicit_c(const ocn_hydro* h) { return h->cv.on && h->cv.disc == 0 && (h->cv.kc != 0.0 || h->cv.kb != 0.0); }
+static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of h->kap (0 u / v, 1 + n tracer n)
+  const ocn_hfield* K = q == 0 ? h->cv.nu : h->cv.kap;
+  return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->cv.t};
+}
+static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q, double dt) {
+  const ocn_hgrid* g = h->lg;
+  dim3 b, gr;
+  hy_cols(g, b, gr);
+  const HyCvSolve s = hydro_cv_solve(h, q);
+  const long sy = f->T[0], sz = (long)f->T[0] * f->T[1];
+  if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else if (loc == 1) ocn_launch(k_hy_cv_implicit<1>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+}
 // update_state!: fills of the prognostic fields, w from continuity, the hydrostatic pressure, fills of w and pHY'
 static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   hfield_fill(h->u);
@@ -1365,6 +1405,7 @@ static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   hfield_fill(h->fs->eta);
   for (ocn_hfield* c : h->c) hfield_fill(c);
   hy_w_launch(h->u, h->v, h->w);
+  if (h->cv.on) hydro_cv_diffusivities(h);
   if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, h->bT >= 0 ? h->c[h->bT] : nullptr, h->bS >= 0 ? h->c[h->bS] : nullptr);
   hfield_fill(h->w);
   hfield_fill(h->pHY);
@@ -1428,24 +1469,65 @@ static void hydro_tendencies(ocn_hydro* h) {
 
 // the explicit horizontal closures: G <- G - (Laplacian + biharmonic term) after the advection kernels (hyclosure.h); nothing is
 // launched for a field whose coefficients are all zero
+// the explicit terms of a ConvectiveAdjustmentVerticalDiffusivity ride in the same pass as new instances (VZ = 1 explicit, 2 the
+// implicit form's w-shear of u and v), summed with the others in tuple order; nothing new is launched without them
 static void hydro_horizontal_closures(ocn_hydro* h) {
-  if (h->kap2.empty()) return;
+  const ocn_hydro::Cavd& cv = h->cv;
+  const int vzu = cv.on && (cv.nuc != 0.0 || cv.nub != 0.0) ? (cv.disc == 1 ? 1 : 2) : 0;
+  const int vzc = cv.on && cv.disc == 1 && (cv.kc != 0.0 || cv.kb != 0.0) ? 1 : 0;
+  if (h->kap2.empty() && !vzu && !vzc) return;
   const ocn_hgrid* g = h->lg;
   const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
   const HyClo m{g->topo[0] != OCN_PERIODIC, g->topo[1] != OCN_PERIODIC, g->j0, g->gNy};
   const ocn_hfield *u = h->u, *v = h->v;
-  const double nu = h->kap2[0], nu4 = h->kap4[0];
+  const double nu = h->kap2.empty() ? 0.0 : h->kap2[0], nu4 = h->kap4.empty() ? 0.0 : h->kap4[0];
+  HyCvTerm zu{}, zc{};
+  if (vzu || vzc) {
+    zu = HyCvTerm{cv.nu->d, h->w->d, (long)cv.nu->T[0], (long)cv.nu->T[0] * cv.nu->T[1], (long)h->w->T[0], (long)h->w->T[0] * h->w->T[1],
+                  cv.order[0], cv.order[1], cv.order[2]};
+    zc = zu;
+    zc.K = cv.kap->d;
+  }
 #define HY_CLO_UV(LAP, BIH)                                                                                                                \
   ocn_launch(k_hy_clo_uv<LAP, BIH>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d, h->gn[0]->d, \
-             h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1])
-  if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(true, true);
+             h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], HyCvTerm{})
+#define HY_CLO_UVZ(LAP, BIH, VZ)                                                                                                           \
+  ocn_launch(k_hy_clo_uv<LAP, BIH, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d,          \
+             h->gn[0]->d, h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], zu)
+#define HY_CLO_UV3(VZ)                                                                                                                     \
+  if (nu != 0.0 && nu4 != 0.0) HY_CLO_UVZ(true, true, VZ);                                                                                 \
+  else if (nu != 0.0) HY_CLO_UVZ(true, false, VZ);                                                                                         \
+  else if (nu4 != 0.0) HY_CLO_UVZ(false, true, VZ);                                                                                        \
+  else HY_CLO_UVZ(false, false, VZ);
+  if (vzu == 1) { HY_CLO_UV3(1) }
+  else if (vzu == 2) { HY_CLO_UV3(2) }
+  else if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(true, true);
   else if (nu != 0.0) HY_CLO_UV(true, false);
   else if (nu4 != 0.0) HY_CLO_UV(false, true);
+#undef HY_CLO_UV3
+#undef HY_CLO_UVZ
 #undef HY_CLO_UV
   for (size_t q = 0; q < h->c.size(); q += 2) {
     const bool two = q + 1 < h->c.size();
-    const double k0 = h->kap2[1 + q], k1 = two ? h->kap2[2 + q] : 0.0, k40 = h->kap4[1 + q], k41 = two ? h->kap4[2 + q] : 0.0;
+    const bool hz = !h->kap2.empty();
+    const double k0 = hz ? h->kap2[1 + q] : 0.0, k1 = hz && two ? h->kap2[2 + q] : 0.0, k40 = hz ? h->kap4[1 + q] : 0.0,
+                 k41 = hz && two ? h->kap4[2 + q] : 0.0;
     const bool lap = k0 != 0.0 || k1 != 0.0, bih = k40 != 0.0 || k41 != 0.0;
+    if (vzc) {
+      const ocn_hfield* c = h->c[q];
+      const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
+      double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
+#define HY_CLO_CZ(LAP, BIH)                                                                                                                \
+  if (two)                                                                                                                                 \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 2, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],          \
+               (long)c->T[0] * c->T[1], zc);                                                                                               \
+  else                                                                                                                                     \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 1, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],          \
+               (long)c->T[0] * c->T[1], zc);
+      if (lap && bih) { HY_CLO_CZ(true, true) } else if (lap) { HY_CLO_CZ(true, false) } else if (bih) { HY_CLO_CZ(false, true) } else { HY_CLO_CZ(false, false) }
+#undef HY_CLO_CZ
+      continue;
+    }
     if (!lap && !bih) continue;
     const ocn_hfield* c = h->c[q];
     const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
@@ -1453,10 +1535,10 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
 #define HY_CLO_C(LAP, BIH)                                                                                                                 \
   if (two)                                                                                                                                 \
     ocn_launch(k_hy_clo_c<LAP, BIH, 2>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
-               (long)c->T[0] * c->T[1]);                                                                                                   \
+               (long)c->T[0] * c->T[1], HyCvTerm{});                                                                                       \
   else                                                                                                                                     \
     ocn_launch(k_hy_clo_c<LAP, BIH, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
-               (long)c->T[0] * c->T[1]);
+               (long)c->T[0] * c->T[1], HyCvTerm{});
     if (lap && bih) { HY_CLO_C(true, true) } else if (lap) { HY_CLO_C(true, false) } else { HY_CLO_C(false, true) }
 #undef HY_CLO_C
   }
@@ -2157,6 +2239,9 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   for (auto& e : h->imptab) hipFree(e.d);
   for (auto& f : h->fbc)
     for (auto& b : f) hipFree(b.d);
+  if (h->cv.kap) ocn_hfield_destroy(h->cv.kap);
+  if (h->cv.nu) ocn_hfield_destroy(h->cv.nu);
+  hipFree(h->cv.t);
   delete h;
   hgrid_release(g);
 }
@@ -2179,10 +2264,17 @@ int ocn_hydro_ab2_step(ocn_hydro* h, double dt, double chi) {
   if (rc) return rc;
   hy_ab2_launch(h->u, h->gn[0], h->gm[0], dt, chi, false);
   hy_ab2_launch(h->v, h->gn[1], h->gm[1], dt, chi, false);
-  if ((rc = hydro_implicit(h, h->u, 0, dt)) || (rc = hydro_implicit(h, h->v, 0, dt))) return rc;
+  if (hydro_cv_implicit_uv(h)) {
+    hydro_cv_implicit_launch(h, h->u, 1, 0, dt);
+    hydro_cv_implicit_launch(h, h->v, 2, 0, dt);
+  } else if ((rc = hydro_implicit(h, h->u, 0, dt)) || (rc = hydro_implicit(h, h->v, 0, dt))) {
+    return rc;
+  }
   for (size_t q = 0; q < h->c.size(); ++q) hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, false);
-  for (size_t q = 0; q < h->c.size(); ++q)
-    if ((rc = hydro_implicit(h, h->c[q], 1 + (int)q, dt))) return rc;
+  for (size_t q = 0; q < h->c.size(); ++q) {
+    if (hydro_cv_implicit_c(h)) hydro_cv_implicit_launch(h, h->c[q], 0, 1 + (int)q, dt);
+    else if ((rc = hydro_implicit(h, h->c[q], 1 + (int)q, dt))) return rc;
+  }
   return ocn_sefs_step(h->fs, h->gn[0], h->gn[1], h->gm[0], h->gm[1], dt, chi);
 }
 
@@ -2205,13 +2297,25 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
   }
   const double cn = 1.5 + chi, cm = 0.5 + chi;
   dim3 blk(64, 4, 1);
-  const bool implicit = hydro_has_implicit(h);
+  const bool cvuv = hydro_cv_implicit_uv(h), cvc = hydro_cv_implicit_c(h);
+  const bool implicit = hydro_has_implicit(h) || cvc;
   HyImp impv{nullptr, nullptr, nullptr, nullptr};
-  const int visc = implicit && h->kap[0] != 0.0;
+  const int visc = !cvuv && hydro_has_implicit(h) && h->kap[0] != 0.0;
   if (visc && (rc = hydro_imp_table(h, h->kap[0], dt, &impv))) return api_done(ctx, rc);
   for (int q = 0; q < 2; ++q) {
     ocn_hfield *f = q ? h->v : h->u, *U = q ? s->V : s->U, *GU = q ? s->GV : s->GU;
     const long off = q ? h->offV : h->offU;
+    if (cvuv) {
+      const HyCvSolve cs = hydro_cv_solve(h, 0);
+#define HY_CV_MOM(LOC)                                                                                                                     \
+  ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d,       \
+             h->gm[q]->d, U->d + off, GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], (long)f->T[0],         \
+             (long)f->T[0] * f->T[1], (long)U->T[0])
+      if (q) HY_CV_MOM(2);
+      else HY_CV_MOM(1);
+#undef HY_CV_MOM
+      continue;
+    }
     ocn_launch(k_hy_momentum, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d, U->d + off,
                GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0], g->H[1],
                g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1], (long)U->T[0], impv, visc);
@@ -2231,7 +2335,14 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
                  (long)T->T[0], (long)T->T[0] * T->T[1]);
       pressure_done = true;
     } else {
-      if (implicit && h->kap[1 + q] != 0.0) {
+      if (cvc) {
+        // explicit step, G^- <- G^n and the closure's per-column solve in one kernel
+        dim3 b2, g2;
+        hy_cols(g, b2, g2);
+        ocn_hfield* f = h->c[q];
+        ocn_launch(k_hy_cv_ab2, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                   hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+      } else if (implicit && (size_t)(1 + q) < h->kap.size() && h->kap[1 + q] != 0.0) {
         // explicit step, G^- <- G^n and the implicit solve in one kernel; the hydrostatic pressure then comes from update_state!'s kernel
         HyImp it;
         if ((rc = hydro_imp_table(h, h->kap[1 + q], dt, &it))) return api_done(ctx, rc);
@@ -2356,6 +2467,82 @@ int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kin
   b.kind = kind;
   b.value = value;
   return OCN_OK;
+}
+
+/* closure = ConvectiveAdjustmentVerticalDiffusivity(discretization; convective_kappaz, convective_nuz, background_kappaz,
+ * background_nuz) (convective_adjustment_vertical_diffusivity.jl), alone or in a tuple; hyconvect.h */
+int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, double convective_kappaz, double convective_nuz,
+                                        double background_kappaz, double background_nuz, int32_t ntuple, const int32_t* tuple) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const double kc = convective_kappaz, nuc = convective_nuz, kb = background_kappaz, nub = background_nuz;
+  if (discretization != 0 && discretization != 1) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: discretization 0 (vertically implicit) or 1 (explicit), got %d", (int)discretization);
+    return OCN_EINVAL;
+  }
+  if (!(kc >= 0 && nuc >= 0 && kb >= 0 && nub >= 0) || !std::isfinite(kc + nuc + kb + nub)) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: diffusivities and viscosities must be finite and >= 0 (%g, %g, %g, %g)", kc, nuc, kb, nub);
+    return OCN_EINVAL;
+  }
+  if (ntuple < 0 || (ntuple > 0 && !tuple)) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a closure tuple of %d entries without its kinds", (int)ntuple);
+    return OCN_EINVAL;
+  }
+  // the kinds of the closure tuple in order (OCN_CLOSURE_*): the explicit terms are summed in that order
+  int order[3], n = 0, ncv = 0, seen[4] = {0, 0, 0, 0};
+  for (int q = 0; q < ntuple; ++q) {
+    const int kind = tuple[q];
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_CONVECTIVE_ADJUSTMENT) {
+      ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: unknown closure kind %d at tuple position %d", kind, q);
+      return OCN_EINVAL;
+    }
+    if (seen[kind]++) {
+      ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a closure tuple holds at most one closure of each kind (kind %d twice%s)", kind,
+                    kind == OCN_CLOSURE_CONVECTIVE_ADJUSTMENT ? ": a second ConvectiveAdjustmentVerticalDiffusivity" : "");
+      return OCN_EINVAL;
+    }
+    ncv += kind == OCN_CLOSURE_CONVECTIVE_ADJUSTMENT;
+    if (kind != OCN_CLOSURE_VERTICAL_SCALAR) order[n++] = kind == OCN_CLOSURE_HORIZONTAL_SCALAR ? 0 : kind == OCN_CLOSURE_HORIZONTAL_BIHARMONIC ? 1 : 2;
+  }
+  if (ntuple > 0 && ncv == 0) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure tuple holds no ConvectiveAdjustmentVerticalDiffusivity");
+    return OCN_EINVAL;
+  }
+  for (int e = 0; e < 3; ++e) {        // kinds the tuple leaves out: zero terms, last
+    bool in = false;
+    for (int q = 0; q < n; ++q) in = in || order[q] == e;
+    if (!in) order[n++] = e;
+  }
+  const bool on = kc != 0.0 || nuc != 0.0 || kb != 0.0 || nub != 0.0;
+  if (on && g->H[2] < 1) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure reads one halo cell in z (the grid has %d)", g->H[2]);
+    return OCN_EINVAL;
+  }
+  if (on && !h->cv.kap) {
+    int rc;
+    if ((rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.kap)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.nu))) return rc;
+    const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
+    if (hipMalloc((void**)&h->cv.t, nt * sizeof(double)) != hipSuccess) {
+      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
+      return OCN_ENOMEM;
+    }
+  }
+  h->cv.on = on;
+  h->cv.disc = discretization;
+  h->cv.kc = kc;
+  h->cv.nuc = nuc;
+  h->cv.kb = kb;
+  h->cv.nub = nub;
+  for (int e = 0; e < 3; ++e) h->cv.order[e] = order[e];
+  return OCN_OK;
+}
+
+/* the closure's diffusivity fields, which 0: kappa, 1: nu -- (Center, Center, Face) fields owned by the handle; NULL before the closure
+ * was first switched on */
+ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which) {
+  if (!h || which < 0 || which > 1) return nullptr;
+  return which == 0 ? h->cv.kap : h->cv.nu;
 }
 
 /* ---- third slice: calculate_tendencies! and the whole time step ---------------------------------------------------------------- */

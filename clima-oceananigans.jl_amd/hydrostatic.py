@@ -338,11 +338,36 @@ class VerticalScalarDiffusivity(_ScalarClosure):
     """VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): the implicit vertical solve inside ab2_step!"""
 
 
-_CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity)
+class ConvectiveAdjustmentVerticalDiffusivity:
+    """ConvectiveAdjustmentVerticalDiffusivity(time_discretization; convective_κz, convective_νz, background_κz, background_νz)
+    (TurbulenceClosures/turbulence_closure_implementations/convective_adjustment_vertical_diffusivity.jl): vertical diffusivity kappa and
+    viscosity nu at (Center, Center, Face), the background values where d_z b >= 0 and the convective ones elsewhere, recomputed by
+    update_state; time_discretization "VerticallyImplicit" (the default) or "Explicit"; numbers only"""
+
+    DISCRETIZATIONS = ("VerticallyImplicit", "Explicit")
+
+    def __init__(self, convective_kappaz=0.0, convective_nuz=0.0, background_kappaz=0.0, background_nuz=0.0, time_discretization="VerticallyImplicit"):
+        if time_discretization not in self.DISCRETIZATIONS:
+            raise ValueError(f"time_discretization must be one of {self.DISCRETIZATIONS}, got {time_discretization!r}")
+        self.convective_kappaz, self.convective_nuz = float(convective_kappaz), float(convective_nuz)
+        self.background_kappaz, self.background_nuz = float(background_kappaz), float(background_nuz)
+        self.time_discretization = time_discretization
+
+    def __repr__(self):
+        return (f"ConvectiveAdjustmentVerticalDiffusivity{{{self.time_discretization}TimeDiscretization}}("
+                f"background_kappaz={self.background_kappaz!r}, convective_kappaz={self.convective_kappaz!r}, "
+                f"background_nuz={self.background_nuz!r}, convective_nuz={self.convective_nuz!r})")
+
+
+_CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
+                  ConvectiveAdjustmentVerticalDiffusivity)
+_KIND_CODE = {VerticalScalarDiffusivity: 0, HorizontalScalarDiffusivity: 1, HorizontalScalarBiharmonicDiffusivity: 2,
+              ConvectiveAdjustmentVerticalDiffusivity: 3}      # OCN_CLOSURE_*
 
 
 def closure_parts(closure):
-    """None | (nu, kappa) | a closure object | a tuple of closure objects -> {kind: object}, at most one object of each kind"""
+    """None | (nu, kappa) | a closure object | a tuple of closure objects -> {kind: object}, at most one object of each kind, in tuple
+    order"""
     if closure is None:
         return {}
     if isinstance(closure, _CLOSURE_KINDS):
@@ -489,7 +514,7 @@ class HydrostaticState:
     def set_closure(self, closure):
         """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one
         closure object | a tuple of them (at most one of each kind): HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
-        VerticalScalarDiffusivity; constant coefficients"""
+        VerticalScalarDiffusivity, ConvectiveAdjustmentVerticalDiffusivity; constant coefficients; explicit terms summed in tuple order"""
         parts = closure_parts(closure)
         names = list(self.tracers)
         PD = C.POINTER(C.c_double)
@@ -504,7 +529,25 @@ class HydrostaticState:
               self.grid.ctx.h)
         nu, k = coeffs(VerticalScalarDiffusivity)
         check(self.lib.ocn_hydro_set_closure(self.h, nu, len(names), k.ctypes.data_as(PD)), self.grid.ctx.h)
+        cv = parts.get(ConvectiveAdjustmentVerticalDiffusivity, ConvectiveAdjustmentVerticalDiffusivity())
+        kinds = [_KIND_CODE[kind] for kind in parts] if ConvectiveAdjustmentVerticalDiffusivity in parts else []
+        tup = (C.c_int32 * max(1, len(kinds)))(*kinds)
+        check(self.lib.ocn_hydro_set_convective_adjustment(self.h, cv.DISCRETIZATIONS.index(cv.time_discretization), cv.convective_kappaz,
+                                                           cv.convective_nuz, cv.background_kappaz, cv.background_nuz, len(kinds), tup),
+              self.grid.ctx.h)
         self.closure = closure
+
+    @property
+    def diffusivity_fields(self):
+        """{"kappa": HField, "nu": HField} of a ConvectiveAdjustmentVerticalDiffusivity (Center, Center, Face; set by update_state), or
+        None before one was first switched on"""
+        hk, hn = self.lib.ocn_hydro_diffusivity_field(self.h, 0), self.lib.ocn_hydro_diffusivity_field(self.h, 1)
+        if not hk:
+            return None
+        if getattr(self, "_diffusivity_fields", None) is None:
+            self._diffusivity_fields = {"kappa": HField(self.grid, (Center, Center, Face), handle=hk),
+                                        "nu": HField(self.grid, (Center, Center, Face), handle=hn)}
+        return self._diffusivity_fields
 
     def set_physics(self, momentum_advection, coriolis, tracer_advection):
         """momentum_advection: None | "VectorInvariantEnstrophyConserving" | "VectorInvariantEnergyConserving" |

@@ -403,6 +403,29 @@ int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_
  * context's stream before it copies, so a step already queued reads the previous values: replacing the array between steps is
  * time-varying forcing. */
 int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kind, double value, const double* host, int64_t n);
+/* closure = ConvectiveAdjustmentVerticalDiffusivity(discretization; convective_kappaz, convective_nuz, background_kappaz, background_nuz)
+ * (TurbulenceClosures/turbulence_closure_implementations/convective_adjustment_vertical_diffusivity.jl), numbers only.  update_state!
+ * (ocn_hydro_update_state and the end of every step) sets its diffusivity fields at faces 1..Nz: kappa = background_kappaz where
+ * d_z b >= 0, convective_kappaz elsewhere, nu alike (no buoyancy: d_z b = 0); one kappa serves every tracer.  discretization 0,
+ * vertically implicit (the reference's default): ab2_step! solves (1 - dt d_z K d_z) f = f* per column for u and v (nu interpolated
+ * to the velocity point) and every tracer (kappa), together with the constant coefficients of ocn_hydro_set_closure; and G^n of u and
+ * v gets the interior-face w-shear term -d_z(Az (-nu d_x w)) / V (d_y w for v) whenever a viscosity is non-zero.  discretization 1,
+ * explicit: G^n gets -div(-K d_z f) for u, v and the tracers.  The explicit terms are summed with those of
+ * ocn_hydro_set_horizontal_closure in the order of the closure tuple: `tuple` lists the kinds of its `ntuple` closures in order
+ * (OCN_CLOSURE_*, each at most once; ntuple 0: this closure alone or in front).  All-zero coefficients (the default) switch it off.
+ * OCN_EINVAL for a negative, NaN or infinite coefficient, a discretization other than 0 / 1, a grid without a halo cell in z, a tuple
+ * with a kind twice (a second convective adjustment) or without this closure. */
+enum {
+  OCN_CLOSURE_VERTICAL_SCALAR = 0,          /* VerticalScalarDiffusivity (ocn_hydro_set_closure) */
+  OCN_CLOSURE_HORIZONTAL_SCALAR = 1,        /* HorizontalScalarDiffusivity */
+  OCN_CLOSURE_HORIZONTAL_BIHARMONIC = 2,    /* HorizontalScalarBiharmonicDiffusivity */
+  OCN_CLOSURE_CONVECTIVE_ADJUSTMENT = 3     /* ConvectiveAdjustmentVerticalDiffusivity */
+};
+int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, double convective_kappaz, double convective_nuz,
+                                        double background_kappaz, double background_nuz, int32_t ntuple, const int32_t* tuple);
+/* diffusivity_fields of that closure: which 0 kappa, 1 nu, (Center, Center, Face) fields owned by the handle (parent arrays with halos:
+ * x / y halos as the reference's fills leave them, face Nz + 1 and the z halos zero); NULL before the closure was first switched on */
+ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
 int ocn_hydro_calculate_tendencies(ocn_hydro* h);
