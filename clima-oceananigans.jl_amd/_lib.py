@@ -169,6 +169,7 @@ def load():
         "ocn_hydro_set_horizontal_closure": (I, [P, D, D, I, PD, PD]),
         "ocn_hydro_set_flux_bc": (I, [P, I, I, I, D, PD, C.c_int64]),
         "ocn_hydro_set_convective_adjustment": (I, [P, I, D, D, D, D, I, C.POINTER(C.c_int32)]),
+        "ocn_hydro_set_ri_based_diffusivity": (I, [P, I, I, I, D, D, D, D, D, D, I, C.POINTER(C.c_int32)]),
         "ocn_hydro_diffusivity_field": (P, [P, I]),
         "ocn_hydro_calculate_tendencies": (I, [P]),
         "ocn_hydro_time_step": (I, [P, D, I]),

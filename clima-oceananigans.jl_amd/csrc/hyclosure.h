@@ -31,9 +31,12 @@ struct HyClo {
 // 0 none (the instances without it), 1 the explicit form (-nu d_z u, -nu d_z v, -kappa d_z c), 2 the implicit form's interior-face
 // w-shear of u and v (-nu d_x w, -nu d_y w; the boundary faces keep the explicit flux).  A tuple sums its closures' terms in tuple
 // order: o[0..2] list the Laplacian (0), biharmonic (1) and convective-adjustment (2) terms in that order, absent terms are zero.
+// VZ 3 and 4 are 1 and 2 with (Center, Center, Center) coefficients (RiBasedVerticalDiffusivity(coefficient_z_location = Center()),
+// hyribased.h): kappa at face K is 0.5 (kappa[K-1] + kappa[K]), nu 0.5 (nu_x[K-1] + nu_x[K]) with nu_x the x (or y) interpolation
+// (closure_kernel_operators.jl:84-92, the z interpolation of the x one); the third term is then that closure's.
 struct HyCvTerm {
-  const double* K;         // nu (u, v) or kappa (tracers), (Center, Center, Face)
-  const double* w;         // VZ == 2
+  const double* K;         // nu (u, v) or kappa (tracers), (Center, Center, Face); (Center, Center, Center) for VZ 3, 4
+  const double* w;         // VZ == 2, 4
   long syk, szk, syw, szw;
   int o0, o1, o2;
 };
@@ -144,9 +147,15 @@ __global__ void __launch_bounds__(256) k_hy_clo_uv(HyMetric g, HyClo m, double n
     const double azu = g.azcc[r], azv = g.azff[r];          // Az^fcf = Az^cc, Az^cff = Az^ff
     auto flux = [&](int e, bool isv) {                       // the flux at face K + e
       const long q = ck + (long)e * z.szk;
-      const double nf = isv ? 0.5 * (z.K[q - z.syk] + z.K[q]) : 0.5 * (z.K[q - 1] + z.K[q]);
+      double nf;
+      if (VZ >= 3) {         // centres K - 1 (q - szk) and K (q)
+        const long d = isv ? z.syk : 1;
+        nf = 0.5 * (0.5 * (z.K[q - z.szk - d] + z.K[q - z.szk]) + 0.5 * (z.K[q - d] + z.K[q]));
+      } else {
+        nf = isv ? 0.5 * (z.K[q - z.syk] + z.K[q]) : 0.5 * (z.K[q - 1] + z.K[q]);
+      }
       const int K = k + 1 + e;
-      if (VZ == 2 && K > 1 && K < Nz + 1) {
+      if ((VZ == 2 || VZ == 4) && K > 1 && K < Nz + 1) {
         const long cw = (i + g.Hx) + (long)r * z.syw + (long)(K - 1 + g.Hz) * z.szw;
         return isv ? -nf * ((z.w[cw] - z.w[cw - z.syw]) / g.dycf[r]) : -nf * ((z.w[cw] - z.w[cw - 1]) / g.dxfc[r]);
       }
@@ -213,7 +222,8 @@ __global__ void __launch_bounds__(256) k_hy_clo_c(HyMetric g, HyClo m, double ka
     if (VZ) {
       // -kappa d_z c at faces k + 1 and k + 2 of this cell (kappa as it is: one kappa serves every tracer)
       const long ck = (i + g.Hx) + (long)r * z.syk + (long)(k + g.Hz) * z.szk;
-      auto flux = [&](int e) { return -z.K[ck + (long)e * z.szk] * ((c[(long)e * szc] - c[(long)(e - 1) * szc]) / g.dzf[k + e]); };
+      auto kf = [&](long q) { return VZ >= 3 ? 0.5 * (z.K[q - z.szk] + z.K[q]) : z.K[q]; };
+      auto flux = [&](int e) { return -kf(ck + (long)e * z.szk) * ((c[(long)e * szc] - c[(long)(e - 1) * szc]) / g.dzf[k + e]); };
       const double az = g.azcc[r];
       T = hy_cv_sum(z, LAP ? T : 0.0, b_, rV * (az * flux(1) - az * flux(0)));
     }

@@ -61,8 +61,10 @@ __global__ void k_hy_cv_diff(HyGrid g, HyBuoy q, double kc, double nuc, double k
   }
 }
 
-// one column of the modified Thomas sweep.  LOC: 0 a tracer (kappa as it is), 1 u (nu along x to Face), 2 v (along y).  ck: the
-// coefficient field's element at face 1 of the column (x / y of the field point); ct: the column's scratch element at level 1
+// one column of the modified Thomas sweep.  LOC: 0 a tracer (kappa as it is), 1 u (nu along x to Face), 2 v (along y); 3, 4, 5 the
+// same with (Center, Center, Center) coefficients (hyribased.h), interpolated to face K from the centres K - 1 and K, after x / y
+// for u / v.  ck: the coefficient field's element at face 1 (or level 1) of the column (x / y of the field point); ct: the column's
+// scratch element at level 1
 template <int LOC>
 struct HyCvCol {
   const HyCvSolve& s;
@@ -76,7 +78,11 @@ struct HyCvCol {
     const double* p = s.K + ck + (long)(K - 1) * s.szk;
     if (LOC == 0) return p[0];
     if (LOC == 1) return 0.5 * (p[-1] + p[0]);
-    return 0.5 * (p[-s.syk] + p[0]);
+    if (LOC == 2) return 0.5 * (p[-s.syk] + p[0]);
+    const double* m = p - s.szk;
+    if (LOC == 3) return 0.5 * (m[0] + p[0]);
+    if (LOC == 4) return 0.5 * (0.5 * (m[-1] + m[0]) + 0.5 * (p[-1] + p[0]));
+    return 0.5 * (0.5 * (m[-s.syk] + m[0]) + 0.5 * (p[-s.syk] + p[0]));
   }
   // -dt kappa / dz^c[kc] / dz^f[kf] of this closure, plus the VerticalScalarDiffusivity's
   __device__ double coef(int K, int kc, int kf) const {
@@ -172,12 +178,13 @@ __global__ void k_hy_cv_momentum(double* u, const double* gn, double* gm, double
   Un[c2] = a2;
 }
 
-// a tracer: AB2 step, G^- <- G^n and this closure's solve in one kernel
+// a tracer: AB2 step, G^- <- G^n and this closure's solve in one kernel (LOC 0, or 3 for (Center, Center, Center) coefficients)
+template <int LOC = 0>
 __global__ void k_hy_cv_ab2(double* f, const double* gn, double* gm, double dt, double cn, double cm, HyCvSolve s, HyGrid g, long sy, long sz) {
   OCN_NO_CONTRACT
   const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
   if (i >= g.Nx || j >= g.Ny) return;
-  HyCvCol<0> col{s, g, dt, (i + g.Hx) + (long)(j + g.Hy) * s.syk + (long)g.Hz * s.szk, i + (long)j * g.Nx, (long)g.Nx * g.Ny};
+  HyCvCol<LOC> col{s, g, dt, (i + g.Hx) + (long)(j + g.Hy) * s.syk + (long)g.Hz * s.szk, i + (long)j * g.Nx, (long)g.Nx * g.Ny};
   long c = (i + g.Hx) + (long)(j + g.Hy) * sy + (long)g.Hz * sz;
   double phi = 0.0;
   for (int k = 0; k < g.Nz; ++k, c += sz) {

@@ -214,10 +214,11 @@ __global__ void k_h_fill_z(double* p, int face, int Nx, int Ny, int Nz, int Hx, 
 
 static int hfield_exchange_y(ocn_hfield* f);
 
-static void hfield_fill(ocn_hfield* f) {
+// zfill false: x / y only (a field with no condition in z: the diffusivity fields of a Face location)
+static void hfield_fill(ocn_hfield* f, bool zfill = true) {
   ocn_hgrid* g = f->g;
   hipStream_t s = g->ctx->stream;
-  if (f->loc[2] != OCN_NOTHING && (g->H[2] > 0 || f->loc[2] == OCN_FACE))
+  if (zfill && f->loc[2] != OCN_NOTHING && (g->H[2] > 0 || f->loc[2] == OCN_FACE))
     ocn_launch(k_h_fill_z, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), dim3(64, 4, 1), s, f->d, f->loc[2] == OCN_FACE ? 1 : 0, g->N[0], g->N[1],
                g->N[2], g->H[0], g->H[1], g->H[2], f->T[0], f->T[1]);
   auto bounded = [&](int d, int sides) {
@@ -1035,6 +1036,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 // ConvectiveAdjustmentVerticalDiffusivity: k_hy_cv_diff, k_hy_cv_implicit, k_hy_cv_momentum, k_hy_cv_ab2 (its explicit terms: hyclosure.h)
 #include "hyconvect.h"
 
+// RiBasedVerticalDiffusivity: k_hy_ri_diff (its solve and explicit terms: hyconvect.h / hyclosure.h with the Center-location variants)
+#include "hyribased.h"
+
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
 // the level only, so the pivots beta_k and the multipliers t_k of the modified Thomas algorithm are tabulated once per (kappa, dt) on
@@ -1220,8 +1224,10 @@ struct ocn_hydro {
   // lives on the device and is kept for reuse when the condition is replaced
   struct FluxBC { int kind = 0; double value = 0.0; double* d = nullptr; };
   std::vector<std::array<FluxBC, 6>> fbc;
-  // ConvectiveAdjustmentVerticalDiffusivity: on, discretization (0 vertically implicit, 1 explicit), coefficients, the order of the
-  // explicit terms in the tuple (0 Laplacian, 1 biharmonic, 2 this closure), its diffusivity fields and the solve's scratch
+  // ConvectiveAdjustmentVerticalDiffusivity (cv) and RiBasedVerticalDiffusivity (rb), at most one of them on: on, discretization
+  // (0 vertically implicit, 1 explicit), coefficients, the order of the explicit terms in the tuple (0 Laplacian, 1 biharmonic, 2 this
+  // closure), its diffusivity fields and the solve's scratch; loc the fields' z location (0 Face, 1 Center: rb only); nzu / nzc a
+  // viscosity / diffusivity that can be non-zero (the terms of u and v / of the tracers run)
   struct Cavd {
     bool on = false;
     int disc = 0;
@@ -1229,7 +1235,11 @@ struct ocn_hydro {
     int order[3] = {0, 1, 2};
     ocn_hfield *kap = nullptr, *nu = nullptr;
     double* t = nullptr;
-  } cv;
+    int loc = 0, taper = 0;
+    bool nzu = false, nzc = false;
+    HyRiParam rp{};
+  } cv, rb;
+  int vk_last = 0;                           // the closure (OCN_CLOSURE_*) whose fields ocn_hydro_diffusivity_field returns
 };
 
 static HyGrid hy_grid(const ocn_hgrid* g) {
@@ -1381,22 +1391,50 @@ static void hydro_cv_diffusivities(ocn_hydro* h) {
              K->T[0], K->T[1], (int)(g->topo[0] != OCN_PERIODIC), (int)(yb && g->wall_lo), (int)(yb && g->wall_hi), (long)K->T[0],
              (long)K->T[0] * K->T[1]);
 }
-// the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient
-static bool hydro_cv_implicit_uv(const ocn_hydro* h) { return h->cv.on && h->cv.disc == 0 && (h->cv.nuc != 0.0 || h->cv.nub != 0.0); }
-static bool hydro_cv_implicit_c(const ocn_hydro* h) { return h->cv.on && h->cv.disc == 0 && (h->cv.kc != 0.0 || h->cv.kb != 0.0); }
-static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of h->kap (0 u / v, 1 + n tracer n)
-  const ocn_hfield* K = q == 0 ? h->cv.nu : h->cv.kap;
-  return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->cv.t};
+// calculate_diffusivities! of the RiBasedVerticalDiffusivity (hyribased.h): the interior columns, then the fills of a Center field
+// in x / y (with the band exchange) and, for a Center location, the no-flux fill in z
+static void hydro_rb_diffusivities(ocn_hydro* h) {
+  const ocn_hgrid* g = h->lg;
+  ocn_hfield *K = h->rb.kap, *N = h->rb.nu, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  const ocn_hfield *u = h->u, *v = h->v, *c = h->c.empty() ? nullptr : h->c[0];
+  dim3 b, gr;
+  hy_cols(g, b, gr);
+  const long sy = c ? c->T[0] : 0, sz = c ? (long)c->T[0] * c->T[1] : 0;
+#define HY_RI(TP)                                                                                                                          \
+  ocn_launch(k_hy_ri_diff<TP>, gr, b, g->ctx->stream, hy_grid(g), h->buoy, h->rb.rp, (const double*)u->d, (const double*)v->d,               \
+             T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, K->d, N->d, (long)u->T[0],    \
+             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], sy, sz, (long)K->T[0], (long)K->T[0] * K->T[1])
+  if (h->rb.taper == 0) HY_RI(0);
+  else if (h->rb.taper == 1) HY_RI(1);
+  else HY_RI(2);
+#undef HY_RI
+  hfield_fill(K, h->rb.loc == 1);
+  hfield_fill(N, h->rb.loc == 1);
 }
+// the variable-coefficient vertical closure that is on (CAVD or RBVD, never both), or null
+static const ocn_hydro::Cavd* hydro_vk(const ocn_hydro* h) { return h->cv.on ? &h->cv : h->rb.on ? &h->rb : nullptr; }
+// the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient
+static bool hydro_cv_implicit_uv(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->disc == 0 && v->nzu; }
+static bool hydro_cv_implicit_c(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->disc == 0 && v->nzc; }
+static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of h->kap (0 u / v, 1 + n tracer n)
+  const ocn_hydro::Cavd* v = hydro_vk(h);
+  const ocn_hfield* K = q == 0 ? v->nu : v->kap;
+  return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, v->t};
+}
+// loc: 0 a tracer, 1 u, 2 v (+ 3 for Center-location coefficients)
 static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q, double dt) {
   const ocn_hgrid* g = h->lg;
   dim3 b, gr;
   hy_cols(g, b, gr);
   const HyCvSolve s = hydro_cv_solve(h, q);
   const long sy = f->T[0], sz = (long)f->T[0] * f->T[1];
+  loc += hydro_vk(h)->loc == 1 ? 3 : 0;
   if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 1) ocn_launch(k_hy_cv_implicit<1>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else if (loc == 2) ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else if (loc == 3) ocn_launch(k_hy_cv_implicit<3>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else if (loc == 4) ocn_launch(k_hy_cv_implicit<4>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  else ocn_launch(k_hy_cv_implicit<5>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
 }
 // update_state!: fills of the prognostic fields, w from continuity, the hydrostatic pressure, fills of w and pHY'
 static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
@@ -1406,6 +1444,7 @@ static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   for (ocn_hfield* c : h->c) hfield_fill(c);
   hy_w_launch(h->u, h->v, h->w);
   if (h->cv.on) hydro_cv_diffusivities(h);
+  if (h->rb.on) hydro_rb_diffusivities(h);
   if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, h->bT >= 0 ? h->c[h->bT] : nullptr, h->bS >= 0 ? h->c[h->bS] : nullptr);
   hfield_fill(h->w);
   hfield_fill(h->pHY);
@@ -1471,10 +1510,13 @@ static void hydro_tendencies(ocn_hydro* h) {
 // launched for a field whose coefficients are all zero
 // the explicit terms of a ConvectiveAdjustmentVerticalDiffusivity ride in the same pass as new instances (VZ = 1 explicit, 2 the
 // implicit form's w-shear of u and v), summed with the others in tuple order; nothing new is launched without them
+// (VZ 3 / 4 for the Center-location coefficients of a RiBasedVerticalDiffusivity)
 static void hydro_horizontal_closures(ocn_hydro* h) {
-  const ocn_hydro::Cavd& cv = h->cv;
-  const int vzu = cv.on && (cv.nuc != 0.0 || cv.nub != 0.0) ? (cv.disc == 1 ? 1 : 2) : 0;
-  const int vzc = cv.on && cv.disc == 1 && (cv.kc != 0.0 || cv.kb != 0.0) ? 1 : 0;
+  static const ocn_hydro::Cavd off{};
+  const ocn_hydro::Cavd& cv = hydro_vk(h) ? *hydro_vk(h) : off;
+  const int zc3 = cv.loc == 1 ? 2 : 0;
+  const int vzu = cv.on && cv.nzu ? (cv.disc == 1 ? 1 : 2) + zc3 : 0;
+  const int vzc = cv.on && cv.disc == 1 && cv.nzc ? 1 + zc3 : 0;
   if (h->kap2.empty() && !vzu && !vzc) return;
   const ocn_hgrid* g = h->lg;
   const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
@@ -1501,6 +1543,8 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
   else HY_CLO_UVZ(false, false, VZ);
   if (vzu == 1) { HY_CLO_UV3(1) }
   else if (vzu == 2) { HY_CLO_UV3(2) }
+  else if (vzu == 3) { HY_CLO_UV3(3) }
+  else if (vzu == 4) { HY_CLO_UV3(4) }
   else if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(true, true);
   else if (nu != 0.0) HY_CLO_UV(true, false);
   else if (nu4 != 0.0) HY_CLO_UV(false, true);
@@ -1517,15 +1561,18 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
       const ocn_hfield* c = h->c[q];
       const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
       double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
-#define HY_CLO_CZ(LAP, BIH)                                                                                                                \
+#define HY_CLO_CZV(LAP, BIH, VZ)                                                                                                           \
   if (two)                                                                                                                                 \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 2, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],          \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 2, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],         \
                (long)c->T[0] * c->T[1], zc);                                                                                               \
   else                                                                                                                                     \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 1, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],          \
+    ocn_launch(k_hy_clo_c<LAP, BIH, 1, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],         \
                (long)c->T[0] * c->T[1], zc);
+#define HY_CLO_CZ(LAP, BIH)                                                                                                                \
+  if (vzc == 3) { HY_CLO_CZV(LAP, BIH, 3) } else { HY_CLO_CZV(LAP, BIH, 1) }
       if (lap && bih) { HY_CLO_CZ(true, true) } else if (lap) { HY_CLO_CZ(true, false) } else if (bih) { HY_CLO_CZ(false, true) } else { HY_CLO_CZ(false, false) }
 #undef HY_CLO_CZ
+#undef HY_CLO_CZV
       continue;
     }
     if (!lap && !bih) continue;
@@ -2239,9 +2286,11 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   for (auto& e : h->imptab) hipFree(e.d);
   for (auto& f : h->fbc)
     for (auto& b : f) hipFree(b.d);
-  if (h->cv.kap) ocn_hfield_destroy(h->cv.kap);
-  if (h->cv.nu) ocn_hfield_destroy(h->cv.nu);
-  hipFree(h->cv.t);
+  for (ocn_hydro::Cavd* v : {&h->cv, &h->rb}) {
+    if (v->kap) ocn_hfield_destroy(v->kap);
+    if (v->nu) ocn_hfield_destroy(v->nu);
+    hipFree(v->t);
+  }
   delete h;
   hgrid_release(g);
 }
@@ -2311,8 +2360,14 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
   ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d,       \
              h->gm[q]->d, U->d + off, GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], (long)f->T[0],         \
              (long)f->T[0] * f->T[1], (long)U->T[0])
-      if (q) HY_CV_MOM(2);
-      else HY_CV_MOM(1);
+      const bool cz = hydro_vk(h)->loc == 1;
+      if (q) {
+        if (cz) HY_CV_MOM(5);
+        else HY_CV_MOM(2);
+      } else {
+        if (cz) HY_CV_MOM(4);
+        else HY_CV_MOM(1);
+      }
 #undef HY_CV_MOM
       continue;
     }
@@ -2340,8 +2395,12 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
         dim3 b2, g2;
         hy_cols(g, b2, g2);
         ocn_hfield* f = h->c[q];
-        ocn_launch(k_hy_cv_ab2, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                   hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+        if (hydro_vk(h)->loc == 1)
+          ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+        else
+          ocn_launch(k_hy_cv_ab2<0>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
       } else if (implicit && (size_t)(1 + q) < h->kap.size() && h->kap[1 + q] != 0.0) {
         // explicit step, G^- <- G^n and the implicit solve in one kernel; the hydrostatic pressure then comes from update_state!'s kernel
         HyImp it;
@@ -2490,11 +2549,16 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
     return OCN_EINVAL;
   }
   // the kinds of the closure tuple in order (OCN_CLOSURE_*): the explicit terms are summed in that order
-  int order[3], n = 0, ncv = 0, seen[4] = {0, 0, 0, 0};
+  int order[3], n = 0, ncv = 0, seen[5] = {0, 0, 0, 0, 0};
   for (int q = 0; q < ntuple; ++q) {
     const int kind = tuple[q];
-    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_CONVECTIVE_ADJUSTMENT) {
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_RI_BASED) {
       ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: unknown closure kind %d at tuple position %d", kind, q);
+      return OCN_EINVAL;
+    }
+    if (kind == OCN_CLOSURE_RI_BASED) {
+      ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a closure tuple holds at most one variable-coefficient vertical closure "
+                    "(ConvectiveAdjustmentVerticalDiffusivity together with RiBasedVerticalDiffusivity)");
       return OCN_EINVAL;
     }
     if (seen[kind]++) {
@@ -2519,6 +2583,10 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure reads one halo cell in z (the grid has %d)", g->H[2]);
     return OCN_EINVAL;
   }
+  if (on && h->rb.on) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a RiBasedVerticalDiffusivity is on (at most one variable-coefficient vertical closure)");
+    return OCN_EINVAL;
+  }
   if (on && !h->cv.kap) {
     int rc;
     if ((rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.kap)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.nu))) return rc;
@@ -2534,15 +2602,123 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
   h->cv.nuc = nuc;
   h->cv.kb = kb;
   h->cv.nub = nub;
+  h->cv.nzu = nuc != 0.0 || nub != 0.0;
+  h->cv.nzc = kc != 0.0 || kb != 0.0;
   for (int e = 0; e < 3; ++e) h->cv.order[e] = order[e];
+  if (on) h->vk_last = OCN_CLOSURE_CONVECTIVE_ADJUSTMENT;
   return OCN_OK;
 }
 
-/* the closure's diffusivity fields, which 0: kappa, 1: nu -- (Center, Center, Face) fields owned by the handle; NULL before the closure
- * was first switched on */
+/* closure = RiBasedVerticalDiffusivity(discretization; coefficient_z_location, Ri_dependent_tapering, nu0, Ri0nu, Ridnu, kappa0, Ri0kappa,
+ * Ridkappa) (ri_based_vertical_diffusivity.jl), alone or in a tuple; hyribased.h */
+int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int32_t location, int32_t tapering, double nu0, double Ri0nu,
+                                       double Ridnu, double kappa0, double Ri0kappa, double Ridkappa, int32_t ntuple, const int32_t* tuple) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const char* fn = "ocn_hydro_set_ri_based_diffusivity";
+  if (discretization != 0 && discretization != 1) {
+    ocn_set_error(ctx, "%s: discretization 0 (vertically implicit) or 1 (explicit), got %d", fn, (int)discretization);
+    return OCN_EINVAL;
+  }
+  if (location != 0 && location != 1) {
+    ocn_set_error(ctx, "%s: coefficient_z_location 0 (Face) or 1 (Center), got %d", fn, (int)location);
+    return OCN_EINVAL;
+  }
+  if (tapering < 0 || tapering > 2) {
+    ocn_set_error(ctx, "%s: Ri_dependent_tapering 0 (PiecewiseLinear), 1 (Exponential) or 2 (HyperbolicTangent), got %d", fn, (int)tapering);
+    return OCN_EINVAL;
+  }
+  if (!(nu0 >= 0 && kappa0 >= 0) || !std::isfinite(nu0) || !std::isfinite(kappa0)) {
+    ocn_set_error(ctx, "%s: nu0 and kappa0 must be finite and >= 0 (%g, %g)", fn, nu0, kappa0);
+    return OCN_EINVAL;
+  }
+  if (!std::isfinite(Ri0nu) || !std::isfinite(Ri0kappa)) {
+    ocn_set_error(ctx, "%s: Ri0nu and Ri0kappa must be finite (%g, %g)", fn, Ri0nu, Ri0kappa);
+    return OCN_EINVAL;
+  }
+  if (!(Ridnu > 0 && Ridkappa > 0) || !std::isfinite(Ridnu) || !std::isfinite(Ridkappa)) {
+    ocn_set_error(ctx, "%s: Ridnu and Ridkappa must be finite and > 0 (%g, %g)", fn, Ridnu, Ridkappa);
+    return OCN_EINVAL;
+  }
+  if (ntuple < 0 || (ntuple > 0 && !tuple)) {
+    ocn_set_error(ctx, "%s: a closure tuple of %d entries without its kinds", fn, (int)ntuple);
+    return OCN_EINVAL;
+  }
+  int order[3], n = 0, nrb = 0, seen[5] = {0, 0, 0, 0, 0};
+  for (int q = 0; q < ntuple; ++q) {
+    const int kind = tuple[q];
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_RI_BASED) {
+      ocn_set_error(ctx, "%s: unknown closure kind %d at tuple position %d", fn, kind, q);
+      return OCN_EINVAL;
+    }
+    if (seen[kind]++) {
+      ocn_set_error(ctx, "%s: a closure tuple holds at most one closure of each kind (kind %d twice)", fn, kind);
+      return OCN_EINVAL;
+    }
+    if (kind == OCN_CLOSURE_CONVECTIVE_ADJUSTMENT) {
+      ocn_set_error(ctx, "%s: a closure tuple holds at most one variable-coefficient vertical closure "
+                    "(RiBasedVerticalDiffusivity together with ConvectiveAdjustmentVerticalDiffusivity)", fn);
+      return OCN_EINVAL;
+    }
+    nrb += kind == OCN_CLOSURE_RI_BASED;
+    if (kind != OCN_CLOSURE_VERTICAL_SCALAR) order[n++] = kind == OCN_CLOSURE_HORIZONTAL_SCALAR ? 0 : kind == OCN_CLOSURE_HORIZONTAL_BIHARMONIC ? 1 : 2;
+  }
+  if (ntuple > 0 && nrb == 0) {
+    ocn_set_error(ctx, "%s: the closure tuple holds no RiBasedVerticalDiffusivity", fn);
+    return OCN_EINVAL;
+  }
+  for (int e = 0; e < 3; ++e) {        // kinds the tuple leaves out: zero terms, last
+    bool in = false;
+    for (int q = 0; q < n; ++q) in = in || order[q] == e;
+    if (!in) order[n++] = e;
+  }
+  const bool on = nu0 != 0.0 || kappa0 != 0.0;
+  if (on && g->H[2] < 1) {
+    ocn_set_error(ctx, "%s: the closure reads one halo cell in z (the grid has %d)", fn, g->H[2]);
+    return OCN_EINVAL;
+  }
+  if (on && h->cv.on) {
+    ocn_set_error(ctx, "%s: a ConvectiveAdjustmentVerticalDiffusivity is on (at most one variable-coefficient vertical closure)", fn);
+    return OCN_EINVAL;
+  }
+  ocn_hydro::Cavd& rb = h->rb;
+  if (on && rb.kap && rb.loc != location) {        // the fields' z extent follows the location: Nz + 1 faces or Nz centres
+    ocn_hfield_destroy(rb.kap);
+    ocn_hfield_destroy(rb.nu);
+    rb.kap = rb.nu = nullptr;
+  }
+  if (on && !rb.kap) {
+    const int lz = location == 1 ? OCN_CENTER : OCN_FACE;
+    int rc;
+    if ((rc = hfield_new(g, OCN_CENTER, OCN_CENTER, lz, &rb.kap)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, lz, &rb.nu))) return rc;
+  }
+  if (on && !rb.t) {
+    const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
+    if (hipMalloc((void**)&rb.t, nt * sizeof(double)) != hipSuccess) {
+      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
+      return OCN_ENOMEM;
+    }
+  }
+  rb.on = on;
+  rb.disc = discretization;
+  if (on) rb.loc = location;
+  rb.taper = tapering;
+  rb.rp = HyRiParam{nu0, Ri0nu, Ridnu, kappa0, Ri0kappa, Ridkappa};
+  rb.nzu = nu0 != 0.0;
+  rb.nzc = kappa0 != 0.0;
+  for (int e = 0; e < 3; ++e) rb.order[e] = order[e];
+  if (on) h->vk_last = OCN_CLOSURE_RI_BASED;
+  return OCN_OK;
+}
+
+/* the diffusivity fields of the variable-coefficient vertical closure switched on last (CAVD or RBVD), which 0: kappa, 1: nu --
+ * (Center, Center, Face) or, for a RiBasedVerticalDiffusivity at Center, (Center, Center, Center) fields owned by the handle; NULL
+ * before either was first switched on */
 ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which) {
   if (!h || which < 0 || which > 1) return nullptr;
-  return which == 0 ? h->cv.kap : h->cv.nu;
+  const ocn_hydro::Cavd& v = h->vk_last == OCN_CLOSURE_RI_BASED ? h->rb : h->cv;
+  return which == 0 ? v.kap : v.nu;
 }
 
 /* ---- third slice: calculate_tendencies! and the whole time step ---------------------------------------------------------------- */

@@ -359,10 +359,41 @@ class ConvectiveAdjustmentVerticalDiffusivity:
                 f"background_nuz={self.background_nuz!r}, convective_nuz={self.convective_nuz!r})")
 
 
+class RiBasedVerticalDiffusivity:
+    """RiBasedVerticalDiffusivity(time_discretization; coefficient_z_location, Ri_dependent_tapering, ν₀, Ri₀ν, Riᵟν, κ₀, Ri₀κ, Riᵟκ)
+    (TurbulenceClosures/turbulence_closure_implementations/ri_based_vertical_diffusivity.jl, the reference's defaults): kappa =
+    kappa0 taper(Ri, Ri0kappa, Ridkappa), nu = nu0 taper(Ri, Ri0nu, Ridnu) from the Richardson number at face k, recomputed by
+    update_state; coefficient_z_location "Face" (fields at (Center, Center, Face)) or "Center" ((Center, Center, Center), still from Ri
+    at face k, as the reference computes it); Ri_dependent_tapering "PiecewiseLinear", "Exponential" or "HyperbolicTangent";
+    time_discretization "VerticallyImplicit" or "Explicit"; numbers only"""
+
+    DISCRETIZATIONS = ("VerticallyImplicit", "Explicit")
+    LOCATIONS = ("Face", "Center")
+    TAPERINGS = ("PiecewiseLinear", "Exponential", "HyperbolicTangent")
+
+    def __init__(self, time_discretization="VerticallyImplicit", coefficient_z_location="Face", Ri_dependent_tapering="Exponential",
+                 nu0=0.92, Ri0nu=-1.34, Ridnu=0.61, kappa0=0.18, Ri0kappa=-0.13, Ridkappa=0.6):
+        for name, value, allowed in (("time_discretization", time_discretization, self.DISCRETIZATIONS),
+                                     ("coefficient_z_location", coefficient_z_location, self.LOCATIONS),
+                                     ("Ri_dependent_tapering", Ri_dependent_tapering, self.TAPERINGS)):
+            if value not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, got {value!r}")
+        self.time_discretization, self.coefficient_z_location = time_discretization, coefficient_z_location
+        self.Ri_dependent_tapering = Ri_dependent_tapering
+        self.nu0, self.Ri0nu, self.Ridnu = float(nu0), float(Ri0nu), float(Ridnu)
+        self.kappa0, self.Ri0kappa, self.Ridkappa = float(kappa0), float(Ri0kappa), float(Ridkappa)
+
+    def __repr__(self):
+        return (f"RiBasedVerticalDiffusivity{{{self.time_discretization}TimeDiscretization}}("
+                f"coefficient_z_location={self.coefficient_z_location}, Ri_dependent_tapering={self.Ri_dependent_tapering}, "
+                f"nu0={self.nu0!r}, Ri0nu={self.Ri0nu!r}, Ridnu={self.Ridnu!r}, "
+                f"kappa0={self.kappa0!r}, Ri0kappa={self.Ri0kappa!r}, Ridkappa={self.Ridkappa!r})")
+
+
 _CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
-                  ConvectiveAdjustmentVerticalDiffusivity)
+                  ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity)
 _KIND_CODE = {VerticalScalarDiffusivity: 0, HorizontalScalarDiffusivity: 1, HorizontalScalarBiharmonicDiffusivity: 2,
-              ConvectiveAdjustmentVerticalDiffusivity: 3}      # OCN_CLOSURE_*
+              ConvectiveAdjustmentVerticalDiffusivity: 3, RiBasedVerticalDiffusivity: 4}      # OCN_CLOSURE_*
 
 
 def closure_parts(closure):
@@ -514,7 +545,8 @@ class HydrostaticState:
     def set_closure(self, closure):
         """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one
         closure object | a tuple of them (at most one of each kind): HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
-        VerticalScalarDiffusivity, ConvectiveAdjustmentVerticalDiffusivity; constant coefficients; explicit terms summed in tuple order"""
+        VerticalScalarDiffusivity, ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity (at most one of the last two);
+        explicit terms summed in tuple order"""
         parts = closure_parts(closure)
         names = list(self.tracers)
         PD = C.POINTER(C.c_double)
@@ -529,24 +561,44 @@ class HydrostaticState:
               self.grid.ctx.h)
         nu, k = coeffs(VerticalScalarDiffusivity)
         check(self.lib.ocn_hydro_set_closure(self.h, nu, len(names), k.ctypes.data_as(PD)), self.grid.ctx.h)
-        cv = parts.get(ConvectiveAdjustmentVerticalDiffusivity, ConvectiveAdjustmentVerticalDiffusivity())
-        kinds = [_KIND_CODE[kind] for kind in parts] if ConvectiveAdjustmentVerticalDiffusivity in parts else []
-        tup = (C.c_int32 * max(1, len(kinds)))(*kinds)
-        check(self.lib.ocn_hydro_set_convective_adjustment(self.h, cv.DISCRETIZATIONS.index(cv.time_discretization), cv.convective_kappaz,
-                                                           cv.convective_nuz, cv.background_kappaz, cv.background_nuz, len(kinds), tup),
-              self.grid.ctx.h)
+        def kinds_of(kind):
+            kinds = [_KIND_CODE[k] for k in parts] if kind in parts else []
+            return len(kinds), (C.c_int32 * max(1, len(kinds)))(*kinds)
+
+        def set_cavd():
+            cv = parts.get(ConvectiveAdjustmentVerticalDiffusivity, ConvectiveAdjustmentVerticalDiffusivity())
+            check(self.lib.ocn_hydro_set_convective_adjustment(self.h, cv.DISCRETIZATIONS.index(cv.time_discretization), cv.convective_kappaz,
+                                                               cv.convective_nuz, cv.background_kappaz, cv.background_nuz,
+                                                               *kinds_of(ConvectiveAdjustmentVerticalDiffusivity)),
+                  self.grid.ctx.h)
+
+        def set_rbvd():
+            rb = parts.get(RiBasedVerticalDiffusivity, RiBasedVerticalDiffusivity(nu0=0.0, kappa0=0.0))
+            check(self.lib.ocn_hydro_set_ri_based_diffusivity(self.h, rb.DISCRETIZATIONS.index(rb.time_discretization),
+                                                              rb.LOCATIONS.index(rb.coefficient_z_location),
+                                                              rb.TAPERINGS.index(rb.Ri_dependent_tapering), rb.nu0, rb.Ri0nu, rb.Ridnu,
+                                                              rb.kappa0, rb.Ri0kappa, rb.Ridkappa, *kinds_of(RiBasedVerticalDiffusivity)),
+                  self.grid.ctx.h)
+        # at most one of the two is on: the one switched off goes first
+        for setter in ((set_cavd, set_rbvd) if RiBasedVerticalDiffusivity in parts else (set_rbvd, set_cavd)):
+            setter()
         self.closure = closure
 
     @property
     def diffusivity_fields(self):
-        """{"kappa": HField, "nu": HField} of a ConvectiveAdjustmentVerticalDiffusivity (Center, Center, Face; set by update_state), or
+        """{"kappa": HField, "nu": HField} of the ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity switched on
+        last ((Center, Center, Face), or (Center, Center, Center) for a RiBasedVerticalDiffusivity at Center; set by update_state), or
         None before one was first switched on"""
         hk, hn = self.lib.ocn_hydro_diffusivity_field(self.h, 0), self.lib.ocn_hydro_diffusivity_field(self.h, 1)
         if not hk:
             return None
-        if getattr(self, "_diffusivity_fields", None) is None:
-            self._diffusivity_fields = {"kappa": HField(self.grid, (Center, Center, Face), handle=hk),
-                                        "nu": HField(self.grid, (Center, Center, Face), handle=hn)}
+        cached = getattr(self, "_diffusivity_fields", None)
+        if cached is None or cached["kappa"].h.value != hk or cached["nu"].h.value != hn:
+            total, interior, halo = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)()
+            check(self.lib.ocn_hfield_shape(C.c_void_p(hk), total, interior, halo), self.grid.ctx.h)
+            lz = Face if interior[2] == self.grid.Nz + 1 else Center
+            self._diffusivity_fields = {"kappa": HField(self.grid, (Center, Center, lz), handle=hk),
+                                        "nu": HField(self.grid, (Center, Center, lz), handle=hn)}
         return self._diffusivity_fields
 
     def set_physics(self, momentum_advection, coriolis, tracer_advection):

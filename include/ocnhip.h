@@ -419,12 +419,28 @@ enum {
   OCN_CLOSURE_VERTICAL_SCALAR = 0,          /* VerticalScalarDiffusivity (ocn_hydro_set_closure) */
   OCN_CLOSURE_HORIZONTAL_SCALAR = 1,        /* HorizontalScalarDiffusivity */
   OCN_CLOSURE_HORIZONTAL_BIHARMONIC = 2,    /* HorizontalScalarBiharmonicDiffusivity */
-  OCN_CLOSURE_CONVECTIVE_ADJUSTMENT = 3     /* ConvectiveAdjustmentVerticalDiffusivity */
+  OCN_CLOSURE_CONVECTIVE_ADJUSTMENT = 3,    /* ConvectiveAdjustmentVerticalDiffusivity */
+  OCN_CLOSURE_RI_BASED = 4                  /* RiBasedVerticalDiffusivity */
 };
 int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, double convective_kappaz, double convective_nuz,
                                         double background_kappaz, double background_nuz, int32_t ntuple, const int32_t* tuple);
-/* diffusivity_fields of that closure: which 0 kappa, 1 nu, (Center, Center, Face) fields owned by the handle (parent arrays with halos:
- * x / y halos as the reference's fills leave them, face Nz + 1 and the z halos zero); NULL before the closure was first switched on */
+/* closure = RiBasedVerticalDiffusivity(discretization; coefficient_z_location, Ri_dependent_tapering, nu0, Ri0nu, Ridnu, kappa0, Ri0kappa,
+ * Ridkappa) (TurbulenceClosures/turbulence_closure_implementations/ri_based_vertical_diffusivity.jl), numbers only.  update_state! sets
+ * kappa = kappa0 taper(Ri, Ri0kappa, Ridkappa) and nu = nu0 taper(Ri, Ri0nu, Ridnu) at k = 1..Nz, with Ri = N^2 / (d_z u^2 + d_z v^2) at
+ * face k (0 where N^2 = 0; +-Inf where N^2 != 0 over zero shear, which every taper maps to exactly 0 or 1) -- at face k for either
+ * location, as the reference has it; one kappa serves every tracer.  location 0 Face (the default): (Center, Center, Face) fields, used
+ * as CAVD's; 1 Center: (Center, Center, Center) fields, interpolated to the faces (0.5 (K[k-1] + K[k]), after x / y for u / v).
+ * tapering 0 PiecewiseLinear, 1 Exponential (the default), 2 HyperbolicTangent.  Discretizations and the closure tuple as for
+ * ocn_hydro_set_convective_adjustment; nu0 = kappa0 = 0 switches it off.  OCN_EINVAL for a negative or non-finite nu0 or kappa0, a
+ * non-finite Ri0, an Rid <= 0 or non-finite, an unknown location, tapering or discretization, a grid without a halo cell in z, a tuple
+ * with a kind twice or without this closure, and a tuple (or a handle) that holds a ConvectiveAdjustmentVerticalDiffusivity too: at
+ * most one variable-coefficient vertical closure is on at a time (ocn_hydro_set_convective_adjustment refuses the converse). */
+int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int32_t location, int32_t tapering, double nu0, double Ri0nu,
+                                       double Ridnu, double kappa0, double Ri0kappa, double Ridkappa, int32_t ntuple, const int32_t* tuple);
+/* diffusivity_fields of the closure above switched on last: which 0 kappa, 1 nu, fields owned by the handle, (Center, Center, Face) or
+ * (Center, Center, Center) for a RiBasedVerticalDiffusivity at Center (parent arrays with halos: x / y halos as the reference's fills
+ * leave them; Face: face Nz + 1 and the z halos zero; Center: the first z halo on either side a copy of the level next to it); NULL
+ * before either closure was first switched on */
 ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
