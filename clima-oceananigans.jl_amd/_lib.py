@@ -173,6 +173,12 @@ def load():
         "ocn_hydro_diffusivity_field": (P, [P, I]),
         "ocn_hydro_calculate_tendencies": (I, [P]),
         "ocn_hydro_time_step": (I, [P, D, I]),
+        "ocn_ifs_create": (I, [P, D, D, D, C.c_int64, C.POINTER(P)]),
+        "ocn_ifs_destroy": (None, [P]),
+        "ocn_ifs_field": (P, [P, I]),
+        "ocn_ifs_iterations": (I, [P, C.POINTER(C.c_int64), PD]),
+        "ocn_ifs_step": (I, [P, P, P, D]),
+        "ocn_hydro_create_implicit": (I, [C.POINTER(HydroDesc), P, C.POINTER(P)]),
         "ocn_profile_enable": (I, [P, I]),
         "ocn_profile_read": (I, [P, C.c_char_p, PD, C.POINTER(C.c_int64)]),
         "ocn_profile_reset": (I, [P]),

@@ -1039,6 +1039,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 // RiBasedVerticalDiffusivity: k_hy_ri_diff (its solve and explicit terms: hyconvect.h / hyclosure.h with the Center-location variants)
 #include "hyribased.h"
 
+// the implicit free surface (ImplicitFreeSurface with the PCG solver)
+#include "hyimplicit.h"
+
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
 // the level only, so the pivots beta_k and the multipliers t_k of the modified Thomas algorithm are tabulated once per (kappa, dt) on
@@ -1199,12 +1202,30 @@ static void vsum(ocn_sefs* s, ocn_hfield* out, const ocn_hfield* a, const ocn_hf
 }
 
 
+// ---- the implicit free surface (hyimplicit.h) ------------------------------------------------------------------------------------
+struct ocn_ifs {
+  ocn_hgrid* g;
+  double grav, reltol, abstol;
+  int maxiter;
+  ocn_hfield *eta, *Qu, *Qv, *Ax, *Ay, *rhs;           // η, ∫ᶻQ, ∫ᶻA, the right-hand side (ocn_ifs_field order)
+  double *r = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;   // residual, L(p), the two buffers of p: (Center, Center) parents
+  double *prr = nullptr, *ppq = nullptr;                // per-block partials of r·r and p·q
+  IfsState* st = nullptr;                               // the solver's scalars (device)
+  IfsState* hst = nullptr;                              // host copy (pinned on the GPU build)
+  int nb = 1;                                           // blocks of the solver kernels
+  int64_t iterations = 0;                               // of the last solve
+  double rnorm = 0.0;                                   // ‖r‖ at the end of the last solve
+  int last_iters = 0;                                   // the first batch of the next solve is sized by it
+};
+
 // ---- the hydrostatic step (second slice) ----------------------------------------------------------------------------------------
 struct ocn_hydro {
   ocn_sefs* fs;
+  ocn_ifs* ifs = nullptr;                    // the implicit free surface instead (fs is then null)
   ocn_hgrid* lg;                             // the grid of the 3-D fields: the free surface's, or a latitude band of it (the free surface is then
                                              // replicated: every rank sub-cycles the whole barotropic problem after one all-gather of U, V, G^U, G^V)
   long offU = 0, offV = 0;                   // first element of the band's rows inside the free surface's (Face, Center) / (Center, Face) arrays
+  long offE = 0;                             // the same inside a (Center, Center) array of the implicit free surface
   ocn_hfield *u, *v, *w, *pHY;
   std::vector<ocn_hfield*> c, gn, gm;        // tracers and the tendencies: entries 0, 1 of gn / gm are u, v; 2.. the tracers
   HyBuoy buoy;
@@ -1440,7 +1461,7 @@ static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q
 static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   hfield_fill(h->u);
   hfield_fill(h->v);
-  hfield_fill(h->fs->eta);
+  hfield_fill(h->ifs ? h->ifs->eta : h->fs->eta);
   for (ocn_hfield* c : h->c) hfield_fill(c);
   hy_w_launch(h->u, h->v, h->w);
   if (h->cv.on) hydro_cv_diffusivities(h);
@@ -1692,6 +1713,242 @@ static bool hydro_has_implicit(const ocn_hydro* h) {
 static bool same_shape(const ocn_hfield* a, const ocn_hfield* b) {
   return a && b && a->g == b->g && a->T[0] == b->T[0] && a->T[1] == b->T[1] && a->T[2] == b->T[2] && a->loc[0] == b->loc[0] &&
          a->loc[1] == b->loc[1] && a->loc[2] == b->loc[2];
+}
+
+static int hydro_local_ab2_step(ocn_hydro* h, double dt, double chi);
+static int hydro_ifs_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused);
+static int hydro_fused_tracers(ocn_hydro* h, double dt, double chi, bool* pressure_done);
+
+// ---- the implicit free surface: host side ----------------------------------------------------------------------------------------
+static IfsGeo ifs_geo(const ocn_ifs* s) {
+  const ocn_hgrid* g = s->g;
+  IfsGeo q;
+  q.Nx = g->N[0]; q.Ny = g->N[1]; q.Hx = g->H[0]; q.Hy = g->H[1]; q.Tx = s->eta->T[0]; q.Ty = s->eta->T[1];
+  q.xper = g->topo[0] == OCN_PERIODIC; q.yper = g->topo[1] == OCN_PERIODIC;
+  q.yfirst = q.xper && !q.yper;             // hfield_fill: non-periodic directions first
+  q.su = s->Qu->T[0]; q.sv = s->Qv->T[0];
+  return q;
+}
+static IfsOp ifs_op(const ocn_ifs* s, double dt) {
+  const ocn_hgrid* g = s->g;
+  IfsOp o;
+  o.Ax = s->Ax->d; o.Ay = s->Ay->d; o.dxfc = g->dxfc; o.dycf = g->dycf; o.azcc = g->azcc; o.r_dxfc = g->r_dxfc; o.r_dycf = g->r_dycf;
+  o.gdt2 = s->grav * (dt * dt);             // g * Δt^2
+  o.r_gdt2 = 1.0 / o.gdt2;
+  return o;
+}
+// sum!(Q, A * u) of one velocity component (A = Ax with arow = Δyᶠᶜ, Ay with Δxᶜᶠ) into the free surface's rows of u's grid (off)
+static void ifs_vsum_launch(ocn_hfield* Q, long off, const ocn_hfield* u, const double* arow) {
+  const ocn_hgrid* g = u->g;
+  dim3 blk(64, 4, 1), gr((u->S[0] + 63) / 64, (u->S[1] + 3) / 4, 1);
+  ocn_launch(k_ifs_vsum, gr, blk, g->ctx->stream, Q->d + off, (const double*)u->d, arow, (const double*)g->dzc, u->S[0], u->S[1], g->N[2], g->H[0],
+             g->H[1], g->H[2], (long)u->T[0], (long)u->T[0] * u->T[1], (long)Q->T[0]);
+}
+// fill_halo_regions!(∫ᶻQ), the right-hand side, solve!(η, ...) and fill_halo_regions!(η) (implicit_free_surface.jl:137-155): the
+// iterations go out in batches, the first sized by the last solve's count, and the host reads the stop flag once per batch
+static int ifs_solve(ocn_ifs* s, double dt) {
+  ocn_ctx* ctx = s->g->ctx;
+  hipStream_t st = ctx->stream;
+  hfield_fill(s->Qu);
+  hfield_fill(s->Qv);
+  hfield_fill(s->eta);                      // the linear operation fills x = η before q = L(x)
+  const IfsGeo geo = ifs_geo(s);
+  const IfsOp op = ifs_op(s, dt);
+  const dim3 gr(s->nb, 1, 1), blk(IFS_NT, 1, 1);
+  ocn_launch(k_ifs_init, gr, blk, st, geo, op, (const double*)s->eta->d, (const double*)s->Qu->d, (const double*)s->Qv->d, s->rhs->d, s->q, s->r,
+             s->prr, s->st, dt, s->grav * dt);
+  int batch = s->last_iters + 1 > 4 ? s->last_iters + 1 : 4;
+  long launched = 0;
+  for (;;) {
+    for (int b = 0; b < batch; ++b) {
+      ocn_launch(k_ifs_pq, gr, blk, st, geo, op, (const double*)s->r, s->p0, s->p1, s->q, (const double*)s->prr, s->ppq, s->st, s->nb, s->reltol,
+                 s->abstol, s->maxiter);
+      ocn_launch(k_ifs_xr, gr, blk, st, geo, s->eta->d, s->r, (const double*)s->p0, (const double*)s->p1, (const double*)s->q, (const double*)s->ppq,
+                 s->prr, s->st, s->nb);
+    }
+    launched += batch;
+    OCN_HIP_CHECK(ctx, hipMemcpyAsync(s->hst, s->st, sizeof(IfsState), hipMemcpyDeviceToHost, st));
+    OCN_HIP_CHECK(ctx, hipStreamSynchronize(st));
+#ifndef OCN_HOST_EMU
+    if (g_ocn_launch_err.err != hipSuccess) return OCN_OK;      // api_done reports it
+#endif
+    if (s->hst->stop) break;
+    if (launched > (long)s->maxiter + 1) {  // the stop test fires at iteration maxiter at the latest
+      ocn_set_error(ctx, "implicit free surface: the PCG solve did not stop after %ld iterations", launched);
+      return OCN_ESTATE;
+    }
+    batch = 8;
+  }
+  s->iterations = s->hst->it;
+  s->rnorm = s->hst->rnorm;
+  s->last_iters = s->hst->it;
+  if (s->hst->nonfinite) {
+    ocn_set_error(ctx, "implicit free surface: the PCG residual norm became %g after %d iterations", s->hst->rnorm, s->hst->it);
+    return OCN_ESTATE;
+  }
+  hfield_fill(s->eta);
+  return OCN_OK;
+}
+// pressure_correct_velocities!(::ImplicitFreeSurfaceHFSM): u -= g Δt ∂x η, v -= g Δt ∂y η over the grid's cells
+static void ifs_correct_launch(ocn_hydro* h, double dt) {
+  const ocn_hgrid* g = h->lg;
+  const ocn_ifs* s = h->ifs;
+  ocn_hfield *u = h->u, *v = h->v;
+  dim3 blk(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);
+  ocn_launch(k_ifs_correct, gr, blk, g->ctx->stream, u->d, v->d, (const double*)s->eta->d + h->offE, (const double*)g->dxfc, (const double*)g->dycf,
+             s->grav * dt, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
+             (long)v->T[0] * v->T[1], (long)s->eta->T[0]);
+}
+// every band's rows of ∫ᶻQ to every other rank (hydro_allgather_rows for the implicit free surface)
+static int ifs_allgather_rows(ocn_hydro* h) {
+  ocn_ifs* s = h->ifs;
+  ocn_hgrid* lg = h->lg;
+  ocn_ctx* c = lg->ctx;
+  if (!lg->slab) return OCN_OK;
+  const int R = c->nranks, nl = lg->N[1], Hy = lg->H[1];
+  const bool per = lg->topo[1] == OCN_PERIODIC;
+  ocn_hfield* fl[2] = {s->Qu, s->Qv};
+  std::vector<CommOp> sends, recvs;
+  for (int p = 0; p < R; ++p) {
+    if (p == c->rank) continue;
+    for (int q = 0; q < 2; ++q) {
+      ocn_hfield* f = fl[q];
+      const bool facey = q == 1 && !per;
+      const size_t T0 = f->T[0];
+      auto rows = [&](int rank) { return (size_t)(nl + ((facey && rank == R - 1) ? 1 : 0)); };   // the wall row belongs to the last band
+      sends.push_back({f->d + (size_t)(Hy + nl * c->rank) * T0, rows(c->rank) * T0 * sizeof(double), p, 10 + q});
+      recvs.push_back({f->d + (size_t)(Hy + nl * p) * T0, rows(p) * T0 * sizeof(double), p, 10 + q});
+    }
+  }
+  return comm_exchange(c, sends, recvs);
+}
+
+// the fused passes over the tracers of ocn_hydro_step_after_tendencies: AB2 step, G^- <- G^n, the implicit solves and, where it can, the
+// hydrostatic pressure (*pressure_done)
+static int hydro_fused_tracers(ocn_hydro* h, double dt, double chi, bool* pressure_done) {
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  int rc;
+  const double cn = 1.5 + chi, cm = 0.5 + chi;
+  const bool cvc = hydro_cv_implicit_c(h);
+  const bool implicit = hydro_has_implicit(h) || cvc;
+  for (size_t q = 0; q < h->c.size(); ++q) {
+    if ((int)q == h->bS && h->bT >= 0 && !implicit) continue;      // stepped together with T
+    if ((int)q == h->bT && !implicit) {
+      dim3 b, gr;
+      hy_cols(g, b, gr);
+      ocn_hfield *T = h->c[q], *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+      ocn_launch(k_hy_tracers, gr, b, ctx->stream, hy_grid(g), h->buoy, T->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, S ? S->d : (double*)nullptr,
+                 S ? (const double*)h->gn[2 + h->bS]->d : (const double*)nullptr, S ? h->gm[2 + h->bS]->d : (double*)nullptr, h->pHY->d, dt, cn, cm,
+                 (long)T->T[0], (long)T->T[0] * T->T[1]);
+      *pressure_done = true;
+    } else {
+      if (cvc) {
+        // explicit step, G^- <- G^n and the closure's per-column solve in one kernel
+        dim3 b2, g2;
+        hy_cols(g, b2, g2);
+        ocn_hfield* f = h->c[q];
+        if (hydro_vk(h)->loc == 1)
+          ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+        else
+          ocn_launch(k_hy_cv_ab2<0>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+      } else if (implicit && (size_t)(1 + q) < h->kap.size() && h->kap[1 + q] != 0.0) {
+        // explicit step, G^- <- G^n and the implicit solve in one kernel; the hydrostatic pressure then comes from update_state!'s kernel
+        HyImp it;
+        if ((rc = hydro_imp_table(h, h->kap[1 + q], dt, &it))) return rc;
+        dim3 b2, g2;
+        hy_cols(g, b2, g2);
+        ocn_hfield* f = h->c[q];
+        ocn_launch(k_hy_ab2_implicit, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, it, g->N[0], g->N[1], g->N[2],
+                   g->H[0], g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
+      } else {
+        hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, true);
+      }
+    }
+  }
+  return OCN_OK;
+}
+
+/* local_ab2_step! (hydrostatic_free_surface_ab2_step.jl:60-130): AB2 steps of u, v and the tracers with their implicit vertical solves */
+static int hydro_local_ab2_step(ocn_hydro* h, double dt, double chi) {
+  int rc;
+  hy_ab2_launch(h->u, h->gn[0], h->gm[0], dt, chi, false);
+  hy_ab2_launch(h->v, h->gn[1], h->gm[1], dt, chi, false);
+  if (hydro_cv_implicit_uv(h)) {
+    hydro_cv_implicit_launch(h, h->u, 1, 0, dt);
+    hydro_cv_implicit_launch(h, h->v, 2, 0, dt);
+  } else if ((rc = hydro_implicit(h, h->u, 0, dt)) || (rc = hydro_implicit(h, h->v, 0, dt))) {
+    return rc;
+  }
+  for (size_t q = 0; q < h->c.size(); ++q) hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, false);
+  for (size_t q = 0; q < h->c.size(); ++q) {
+    if (hydro_cv_implicit_c(h)) hydro_cv_implicit_launch(h, h->c[q], 0, 1 + (int)q, dt);
+    else if ((rc = hydro_implicit(h, h->c[q], 1 + (int)q, dt))) return rc;
+  }
+  return OCN_OK;
+}
+
+// time_step! from ab2_step! on for the implicit free surface: the steps of u, v (∫ᶻQ summed in the same pass) and the tracers, the
+// free-surface solve, the correction, G^- <- G^n, update_state!.  fused = 0 issues the reference's kernels one by one (the same bits)
+static int hydro_ifs_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused) {
+  ocn_ifs* s = h->ifs;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  int rc;
+  if (!fused && g->slab) fused = 1;
+  if (!fused) {
+    if ((rc = ocn_hydro_ab2_step(h, dt, chi))) return rc;
+    ifs_correct_launch(h, dt);
+    for (size_t q = 0; q < h->gn.size(); ++q) hy_store_launch(h->gm[q], h->gn[q]);
+    hydro_update_state(h, false);
+    return api_done(ctx, OCN_OK);
+  }
+  const double cn = 1.5 + chi, cm = 0.5 + chi;
+  dim3 blk(64, 4, 1);
+  const bool cvuv = hydro_cv_implicit_uv(h);
+  HyImp impv{nullptr, nullptr, nullptr, nullptr};
+  const int visc = !cvuv && hydro_has_implicit(h) && h->kap[0] != 0.0;
+  if (visc && (rc = hydro_imp_table(h, h->kap[0], dt, &impv))) return api_done(ctx, rc);
+  for (int q = 0; q < 2; ++q) {
+    ocn_hfield *f = q ? h->v : h->u, *Q = q ? s->Qv : s->Qu;
+    const long off = q ? h->offV : h->offU;
+    const double* arow = q ? g->dxcf : g->dyfc;
+    if (cvuv) {
+      // the closure's per-column solve as on the split-explicit path (its three column sums land in Q and are overwritten), then ∫ᶻQ
+      const HyCvSolve cs = hydro_cv_solve(h, 0);
+#define HY_CV_MOM(LOC)                                                                                                                     \
+  ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d,       \
+             h->gm[q]->d, Q->d + off, Q->d + off, Q->d + off, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], (long)f->T[0], (long)f->T[0] * f->T[1], \
+             (long)Q->T[0])
+      const bool cz = hydro_vk(h)->loc == 1;
+      if (q) {
+        if (cz) HY_CV_MOM(5);
+        else HY_CV_MOM(2);
+      } else {
+        if (cz) HY_CV_MOM(4);
+        else HY_CV_MOM(1);
+      }
+#undef HY_CV_MOM
+      ifs_vsum_launch(Q, off, f, arow);
+      continue;
+    }
+    ocn_launch(k_hy_momentum_ifs, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d,
+               Q->d + off, arow, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)f->T[0],
+               (long)f->T[0] * f->T[1], (long)Q->T[0], impv, visc);
+  }
+  // fill_halo_regions!(velocities) of implicit_free_surface_step!: the stepped faces on a wall become zero before the correction (∫ᶻQ,
+  // summed above, has its wall faces zeroed by its own fill)
+  hfield_fill(h->u);
+  hfield_fill(h->v);
+  if ((rc = ifs_allgather_rows(h))) return api_done(ctx, rc);
+  bool pressure_done = false;
+  if ((rc = hydro_fused_tracers(h, dt, chi, &pressure_done))) return api_done(ctx, rc);
+  if ((rc = ifs_solve(s, dt))) return api_done(ctx, rc);
+  ifs_correct_launch(h, dt);
+  hydro_update_state(h, pressure_done);
+  return api_done(ctx, OCN_OK);
 }
 
 extern "C" {
@@ -2206,10 +2463,11 @@ int ocn_hydro_pressure(ocn_hfield* pHY, int kind, double g, double alpha, double
   return api_done(hg->ctx, OCN_OK);
 }
 
-int ocn_hydro_create(const ocn_hydro_desc* d, ocn_hydro** out) {
-  if (!d || !out || !d->free_surface || !d->u || !d->v || !d->w || !d->pHY || d->ntracers < 0 || (d->ntracers > 0 && !d->tracers) || !d->Gn || !d->Gm)
+// the model on the split-explicit free surface fs or the implicit one ifs (exactly one of them)
+static int hydro_create(const ocn_hydro_desc* d, ocn_sefs* fs, ocn_ifs* ifs, ocn_hydro** out) {
+  if (!d || !out || (!fs && !ifs) || !d->u || !d->v || !d->w || !d->pHY || d->ntracers < 0 || (d->ntracers > 0 && !d->tracers) || !d->Gn || !d->Gm)
     return OCN_EINVAL;
-  ocn_hgrid* fg = d->free_surface->g;
+  ocn_hgrid* fg = fs ? fs->g : ifs->g;
   ocn_hgrid* g = d->u->g;                        // the grid of the 3-D fields
   ocn_ctx* ctx = fg->ctx;
   if (g != fg) {
@@ -2252,11 +2510,13 @@ int ocn_hydro_create(const ocn_hydro_desc* d, ocn_hydro** out) {
     return OCN_EINVAL;
   }
   ocn_hydro* h = new ocn_hydro;
-  h->fs = d->free_surface;
+  h->fs = fs;
+  h->ifs = ifs;
   h->lg = g;
   const long drow = (long)(g->j0 - fg->j0) + fg->H[1] - g->H[1];      // parent row of the free surface's arrays holding the model's parent row 0
-  h->offU = drow * h->fs->U->T[0];
-  h->offV = drow * h->fs->V->T[0];
+  h->offU = drow * (fs ? fs->U->T[0] : ifs->Qu->T[0]);
+  h->offV = drow * (fs ? fs->V->T[0] : ifs->Qv->T[0]);
+  h->offE = drow * (fs ? fs->eta->T[0] : ifs->eta->T[0]);
   h->u = d->u; h->v = d->v; h->w = d->w; h->pHY = d->pHY;
   h->c.assign(d->tracers, d->tracers + d->ntracers);
   h->gn.assign(d->Gn, d->Gn + 2 + d->ntracers);
@@ -2264,16 +2524,32 @@ int ocn_hydro_create(const ocn_hydro_desc* d, ocn_hydro** out) {
   h->buoy = HyBuoy{kind, d->gravitational_acceleration, d->thermal_expansion, d->haline_contraction};
   h->bT = kind >= 1 ? d->T_index : -1;
   h->bS = kind == 2 ? d->S_index : -1;
-  if (hipMalloc((void**)&h->Un, h->fs->U->n * sizeof(double)) != hipSuccess || hipMalloc((void**)&h->Vn, h->fs->V->n * sizeof(double)) != hipSuccess) {
-    hipFree(h->Un);
-    delete h;
-    return OCN_ENOMEM;
+  if (fs) {
+    if (hipMalloc((void**)&h->Un, h->fs->U->n * sizeof(double)) != hipSuccess || hipMalloc((void**)&h->Vn, h->fs->V->n * sizeof(double)) != hipSuccess) {
+      hipFree(h->Un);
+      delete h;
+      return OCN_ENOMEM;
+    }
+    OCN_ASYNC(hipMemsetAsync(h->Un, 0, h->fs->U->n * sizeof(double), ctx->stream));
+    OCN_ASYNC(hipMemsetAsync(h->Vn, 0, h->fs->V->n * sizeof(double), ctx->stream));
   }
-  OCN_ASYNC(hipMemsetAsync(h->Un, 0, h->fs->U->n * sizeof(double), ctx->stream));
-  OCN_ASYNC(hipMemsetAsync(h->Vn, 0, h->fs->V->n * sizeof(double), ctx->stream));
   g->refs += 1;
   *out = h;
   return OCN_OK;
+}
+
+int ocn_hydro_create(const ocn_hydro_desc* d, ocn_hydro** out) {
+  if (!d || !d->free_surface) return OCN_EINVAL;
+  return hydro_create(d, d->free_surface, nullptr, out);
+}
+
+int ocn_hydro_create_implicit(const ocn_hydro_desc* d, ocn_ifs* free_surface, ocn_hydro** out) {
+  if (!d || !free_surface || !out) return OCN_EINVAL;
+  if (d->free_surface) {
+    ocn_set_error(free_surface->g->ctx, "ocn_hydro_create_implicit: desc->free_surface must be NULL (the implicit free surface is the second argument)");
+    return OCN_EINVAL;
+  }
+  return hydro_create(d, nullptr, free_surface, out);
 }
 
 void ocn_hydro_destroy(ocn_hydro* h) {
@@ -2298,7 +2574,7 @@ void ocn_hydro_destroy(ocn_hydro* h) {
 int ocn_hydro_update_state(ocn_hydro* h) {
   if (!h) return OCN_EINVAL;
   hydro_update_state(h, false);
-  return api_done(h->fs->g->ctx, OCN_OK);
+  return api_done(h->lg->ctx, OCN_OK);
 }
 
 /* ab2_step!(model, dt, chi) as the reference issues it: barotropic mode of the velocities, AB2 steps of u, v and the tracers, then
@@ -2309,29 +2585,29 @@ int ocn_hydro_ab2_step(ocn_hydro* h, double dt, double chi) {
     ocn_set_error(h->lg->ctx, "a model on latitude bands steps through ocn_hydro_step_after_tendencies(fused = 1) / ocn_hydro_time_step only");
     return OCN_EUNSUPPORTED;
   }
-  int rc = ocn_sefs_barotropic_mode(h->fs, h->u, h->v, 0);
+  int rc;
+  if (h->ifs) {
+    // local_ab2_step!, then implicit_free_surface_step! from the stepped velocities
+    if ((rc = hydro_local_ab2_step(h, dt, chi))) return rc;
+    hfield_fill(h->u);                     // fill_halo_regions!(velocities): zeroes the faces on the walls before the correction
+    hfield_fill(h->v);
+    ifs_vsum_launch(h->ifs->Qu, 0, h->u, h->lg->dyfc);
+    ifs_vsum_launch(h->ifs->Qv, 0, h->v, h->lg->dxcf);
+    return api_done(h->lg->ctx, ifs_solve(h->ifs, dt));
+  }
+  rc = ocn_sefs_barotropic_mode(h->fs, h->u, h->v, 0);
   if (rc) return rc;
-  hy_ab2_launch(h->u, h->gn[0], h->gm[0], dt, chi, false);
-  hy_ab2_launch(h->v, h->gn[1], h->gm[1], dt, chi, false);
-  if (hydro_cv_implicit_uv(h)) {
-    hydro_cv_implicit_launch(h, h->u, 1, 0, dt);
-    hydro_cv_implicit_launch(h, h->v, 2, 0, dt);
-  } else if ((rc = hydro_implicit(h, h->u, 0, dt)) || (rc = hydro_implicit(h, h->v, 0, dt))) {
-    return rc;
-  }
-  for (size_t q = 0; q < h->c.size(); ++q) hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, false);
-  for (size_t q = 0; q < h->c.size(); ++q) {
-    if (hydro_cv_implicit_c(h)) hydro_cv_implicit_launch(h, h->c[q], 0, 1 + (int)q, dt);
-    else if ((rc = hydro_implicit(h, h->c[q], 1 + (int)q, dt))) return rc;
-  }
+  if ((rc = hydro_local_ab2_step(h, dt, chi))) return rc;
   return ocn_sefs_step(h->fs, h->gn[0], h->gn[1], h->gm[0], h->gm[1], dt, chi);
 }
+
 
 /* time_step! from ab2_step! on (quasi_adams_bashforth_2.jl:94-100): the step, the barotropic correction of the velocities,
  * G^- <- G^n, update_state!.  fused = 0: kernel by kernel as the reference; 1: the passes over the 3-D fields merged
  * (k_hy_momentum, k_hy_tracers), which leaves the same bits in every field, halos included. */
 int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused) {
   if (!h) return OCN_EINVAL;
+  if (h->ifs) return hydro_ifs_step_after_tendencies(h, dt, chi, fused);
   ocn_sefs* s = h->fs;
   ocn_hgrid* g = h->lg;
   ocn_ctx* ctx = g->ctx;
@@ -2346,8 +2622,7 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
   }
   const double cn = 1.5 + chi, cm = 0.5 + chi;
   dim3 blk(64, 4, 1);
-  const bool cvuv = hydro_cv_implicit_uv(h), cvc = hydro_cv_implicit_c(h);
-  const bool implicit = hydro_has_implicit(h) || cvc;
+  const bool cvuv = hydro_cv_implicit_uv(h);
   HyImp impv{nullptr, nullptr, nullptr, nullptr};
   const int visc = !cvuv && hydro_has_implicit(h) && h->kap[0] != 0.0;
   if (visc && (rc = hydro_imp_table(h, h->kap[0], dt, &impv))) return api_done(ctx, rc);
@@ -2379,42 +2654,7 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
   hfield_fill(s->U);
   hfield_fill(s->V);
   bool pressure_done = false;
-  for (size_t q = 0; q < h->c.size(); ++q) {
-    if ((int)q == h->bS && h->bT >= 0 && !implicit) continue;      // stepped together with T
-    if ((int)q == h->bT && !implicit) {
-      dim3 b, gr;
-      hy_cols(g, b, gr);
-      ocn_hfield *T = h->c[q], *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
-      ocn_launch(k_hy_tracers, gr, b, ctx->stream, hy_grid(g), h->buoy, T->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, S ? S->d : (double*)nullptr,
-                 S ? (const double*)h->gn[2 + h->bS]->d : (const double*)nullptr, S ? h->gm[2 + h->bS]->d : (double*)nullptr, h->pHY->d, dt, cn, cm,
-                 (long)T->T[0], (long)T->T[0] * T->T[1]);
-      pressure_done = true;
-    } else {
-      if (cvc) {
-        // explicit step, G^- <- G^n and the closure's per-column solve in one kernel
-        dim3 b2, g2;
-        hy_cols(g, b2, g2);
-        ocn_hfield* f = h->c[q];
-        if (hydro_vk(h)->loc == 1)
-          ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
-        else
-          ocn_launch(k_hy_cv_ab2<0>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
-      } else if (implicit && (size_t)(1 + q) < h->kap.size() && h->kap[1 + q] != 0.0) {
-        // explicit step, G^- <- G^n and the implicit solve in one kernel; the hydrostatic pressure then comes from update_state!'s kernel
-        HyImp it;
-        if ((rc = hydro_imp_table(h, h->kap[1 + q], dt, &it))) return api_done(ctx, rc);
-        dim3 b2, g2;
-        hy_cols(g, b2, g2);
-        ocn_hfield* f = h->c[q];
-        ocn_launch(k_hy_ab2_implicit, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, it, g->N[0], g->N[1], g->N[2],
-                   g->H[0], g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
-      } else {
-        hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, true);
-      }
-    }
-  }
+  if ((rc = hydro_fused_tracers(h, dt, chi, &pressure_done))) return api_done(ctx, rc);
   // the free surface: G^U, G^V are in place
   for (ocn_hfield* f : {s->etabar, s->Ubar, s->Vbar}) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
   if ((rc = sefs_step_tail(s, dt))) return api_done(ctx, rc);
@@ -2763,13 +3003,13 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
   hydro_flux_bcs(h);
-  return api_done(h->fs->g->ctx, OCN_OK);
+  return api_done(h->lg->ctx, OCN_OK);
 }
 
 /* time_step!(model, dt; euler) (TimeSteppers/quasi_adams_bashforth_2.jl:70-104) */
 int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
   if (!h) return OCN_EINVAL;
-  ocn_ctx* ctx = h->fs->g->ctx;
+  ocn_ctx* ctx = h->lg->ctx;
   const double chi = euler ? -0.5 : h->chi;
   if (euler)
     for (ocn_hfield* f : h->gm) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
@@ -2777,6 +3017,133 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
   hydro_horizontal_closures(h);
   hydro_flux_bcs(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
+}
+
+/* ---- ImplicitFreeSurface(solver_method = :PreconditionedConjugateGradient, preconditioner = nothing) (hyimplicit.h) -------------- */
+int ocn_ifs_create(ocn_hgrid* g, double gravitational_acceleration, double reltol, double abstol, int64_t maxiter, ocn_ifs** out) {
+  if (!g || !out) return OCN_EINVAL;
+  ocn_ctx* ctx = g->ctx;
+  if (g->slab || g->overlap > 0) {
+    ocn_set_error(ctx, "ocn_ifs_create: the implicit free surface lives on the whole grid (every rank solves all of it); pass the unpartitioned grid");
+    return OCN_EINVAL;
+  }
+  if (!(reltol >= 0) || !(abstol >= 0) || !std::isfinite(reltol) || !std::isfinite(abstol) || maxiter < 0 ||
+      !(gravitational_acceleration > 0) || !std::isfinite(gravitational_acceleration)) {
+    ocn_set_error(ctx, "ocn_ifs_create: reltol and abstol must be finite and >= 0, maxiter >= 0, the gravitational acceleration finite and > 0");
+    return OCN_EINVAL;
+  }
+  if ((long)(g->N[0] + 2 * g->H[0] + 1) * (g->N[1] + 2 * g->H[1] + 1) > 0x7fffffffL) {
+    ocn_set_error(ctx, "ocn_ifs_create: the 2-D fields of this grid exceed 2^31 cells");
+    return OCN_EINVAL;
+  }
+  if (g->H[0] < 1 || g->H[1] < 1) {
+    ocn_set_error(ctx, "ocn_ifs_create: needs one halo cell in x and y");
+    return OCN_EINVAL;
+  }
+  for (int d = 0; d < 2; ++d)
+    if (g->topo[d] == OCN_PERIODIC && g->N[d] < g->H[d]) {
+      ocn_set_error(ctx, "ocn_ifs_create: a Periodic direction needs at least as many cells as halo cells");
+      return OCN_EINVAL;
+    }
+  ocn_ifs* s = new ocn_ifs;
+  s->g = g;
+  g->refs += 1;
+  s->grav = gravitational_acceleration;
+  s->reltol = reltol;
+  s->abstol = abstol;
+  s->maxiter = maxiter > 0x7fffffff ? 0x7fffffff : (int)maxiter;
+  struct { ocn_hfield** f; int lx, ly; } tab[] = {{&s->eta, OCN_CENTER, OCN_CENTER}, {&s->Qu, OCN_FACE, OCN_CENTER}, {&s->Qv, OCN_CENTER, OCN_FACE},
+                                                  {&s->Ax, OCN_FACE, OCN_CENTER},    {&s->Ay, OCN_CENTER, OCN_FACE}, {&s->rhs, OCN_CENTER, OCN_CENTER}};
+  for (auto& t : tab) *t.f = nullptr;
+  for (auto& t : tab)
+    if (int rc = hfield_new(g, t.lx, t.ly, OCN_NOTHING, t.f)) {
+      ocn_ifs_destroy(s);
+      return rc;
+    }
+  const size_t n = s->eta->n;
+  bool ok = true;
+  for (double** a : {&s->r, &s->q, &s->p0, &s->p1}) {
+    ok = ok && hipMalloc((void**)a, n * sizeof(double)) == hipSuccess;
+    if (ok) OCN_ASYNC(hipMemsetAsync(*a, 0, n * sizeof(double), ctx->stream));
+  }
+  ok = ok && hipMalloc((void**)&s->prr, IFS_NBMAX * sizeof(double)) == hipSuccess && hipMalloc((void**)&s->ppq, IFS_NBMAX * sizeof(double)) == hipSuccess &&
+       hipMalloc((void**)&s->st, sizeof(IfsState)) == hipSuccess;
+  if (!ok) {
+    ocn_ifs_destroy(s);
+    ocn_set_error(ctx, "ocn_ifs_create: allocation failed");
+    return OCN_ENOMEM;
+  }
+  OCN_ASYNC(hipMemsetAsync(s->st, 0, sizeof(IfsState), ctx->stream));
+  s->hst = new IfsState();
+  const long nbw = (long)((n + IFS_NT * 2 - 1) / (IFS_NT * 2));          // about two parent cells per thread
+  s->nb = nbw < 1 ? 1 : nbw > IFS_NBMAX ? IFS_NBMAX : (int)nbw;
+  // ∫ᶻ_Axᶠᶜᶜ = sum!(Axᶠᶜᶜ), ∫ᶻ_Ayᶜᶠᶜ = sum!(Ayᶜᶠᶜ) over k (level 1 first), then fill_halo_regions! (compute_vertically_integrated_variables.jl)
+  for (int q = 0; q < 2; ++q) {
+    ocn_hfield* f = q ? s->Ay : s->Ax;
+    const std::vector<double>& m = q ? g->h_dxcf : g->h_dyfc;
+    std::vector<double> h(f->n, 0.0);
+    for (int j = 0; j < f->S[1]; ++j)
+      for (int i = 0; i < f->S[0]; ++i) {
+        double acc = 0.0;
+        for (int k = 0; k < g->N[2]; ++k) acc = k == 0 ? m[j + g->H[1]] * g->h_dzc[0] : acc + m[j + g->H[1]] * g->h_dzc[k];
+        h[(i + g->H[0]) + (size_t)(j + g->H[1]) * f->T[0]] = acc;
+      }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(f->d, h.data(), f->n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      ocn_ifs_destroy(s);
+      return OCN_EHIP;
+    }
+    hfield_fill(f);
+  }
+  *out = s;
+  return api_done(ctx, OCN_OK);
+}
+
+void ocn_ifs_destroy(ocn_ifs* s) {
+  if (!s) return;
+  hipStreamSynchronize(s->g->ctx->stream);
+  ocn_hgrid* g = s->g;
+  for (ocn_hfield* f : {s->eta, s->Qu, s->Qv, s->Ax, s->Ay, s->rhs})
+    if (f) {
+      hipFree(f->d);
+      delete f;
+      hgrid_release(g);          // the reference hfield_new took
+    }
+  for (void* a : {(void*)s->r, (void*)s->q, (void*)s->p0, (void*)s->p1, (void*)s->prr, (void*)s->ppq, (void*)s->st}) hipFree(a);
+  delete s->hst;
+  delete s;
+  hgrid_release(g);
+}
+
+ocn_hfield* ocn_ifs_field(ocn_ifs* s, int which) {
+  if (!s) return nullptr;
+  ocn_hfield* tab[] = {s->eta, s->Qu, s->Qv, s->Ax, s->Ay, s->rhs};
+  return (which >= 0 && which < 6) ? tab[which] : nullptr;
+}
+
+int ocn_ifs_iterations(const ocn_ifs* s, int64_t* iterations, double* residual_norm) {
+  if (!s) return OCN_EINVAL;
+  if (iterations) *iterations = s->iterations;
+  if (residual_norm) *residual_norm = s->rnorm;
+  return OCN_OK;
+}
+
+int ocn_ifs_step(ocn_ifs* s, ocn_hfield* u, ocn_hfield* v, double dt) {
+  if (!s || !u || !v) return OCN_EINVAL;
+  ocn_hgrid* g = s->g;
+  if (!is_loc(u, g, OCN_FACE, OCN_CENTER, OCN_CENTER) || !is_loc(v, g, OCN_CENTER, OCN_FACE, OCN_CENTER)) {
+    ocn_set_error(g->ctx, "ocn_ifs_step: u must be a (Face, Center, Center) and v a (Center, Face, Center) field of the free surface's grid");
+    return OCN_EINVAL;
+  }
+  if (!(dt > 0) || !std::isfinite(dt)) {
+    ocn_set_error(g->ctx, "ocn_ifs_step: dt must be finite and > 0");
+    return OCN_EINVAL;
+  }
+  // implicit_free_surface_step!: fill_halo_regions!(velocities), ∫ᶻQ, then the solve
+  hfield_fill(u);
+  hfield_fill(v);
+  ifs_vsum_launch(s->Qu, 0, u, g->dyfc);
+  ifs_vsum_launch(s->Qv, 0, v, g->dxcf);
+  return api_done(g->ctx, ifs_solve(s, dt));
 }
 
 }  // extern "C"

@@ -275,6 +275,99 @@ class SplitExplicitFreeSurface:
             pass
 
 
+_IFS_FIELDS = (("η", (Center, Center)), ("∫ᶻQ.u", (Face, Center)), ("∫ᶻQ.v", (Center, Face)), ("∫ᶻ_Axᶠᶜᶜ", (Face, Center)),
+               ("∫ᶻ_Ayᶜᶠᶜ", (Center, Face)), ("rhs", (Center, Center)))
+_IFS_ASCII = {"η": "eta", "∫ᶻQ.u": "Qu", "∫ᶻQ.v": "Qv", "∫ᶻ_Axᶠᶜᶜ": "Ax", "∫ᶻ_Ayᶜᶠᶜ": "Ay", "rhs": "rhs"}
+DEFAULT = "default"        # ImplicitFreeSurface(preconditioner=DEFAULT): the reference's default preconditioner for the grid
+
+
+class ImplicitFreeSurface:
+    """ImplicitFreeSurface(grid; solver_method = :PreconditionedConjugateGradient, gravitational_acceleration, reltol, abstol, maxiter,
+    preconditioner = nothing) (Models/HydrostaticFreeSurfaceModels/implicit_free_surface.jl, pcg_implicit_free_surface_solver.jl): the
+    free surface solved for implicitly by an unpreconditioned conjugate gradient.  None takes the reference's default: reltol =
+    min(1e-7, 10 sqrt(eps)) = 1e-7, maxiter = Nx Ny.  On a latitude band the free surface lives on the whole grid.  The reference's
+    default solver_method, the other solvers and every preconditioner are refused with a ValueError; on an HRectilinearGrid (where the
+    reference's default preconditioner is its FFT solver) pass preconditioner=None."""
+
+    SOLVERS = ("PreconditionedConjugateGradient",)
+
+    def __init__(self, grid, gravitational_acceleration=g_Earth, solver_method="PreconditionedConjugateGradient", reltol=None, abstol=0.0,
+                 maxiter=None, preconditioner=DEFAULT):
+        sm = str(solver_method).lstrip(":")
+        if sm == "Default":
+            raise ValueError("ImplicitFreeSurface: solver_method :Default is out of scope (it selects :HeptadiagonalIterativeSolver on a "
+                             "LatitudeLongitudeGrid and :FastFourierTransform on a regular RectilinearGrid); pass "
+                             "solver_method='PreconditionedConjugateGradient'")
+        if sm in ("HeptadiagonalIterativeSolver", "FastFourierTransform", "Multigrid"):
+            raise ValueError(f"ImplicitFreeSurface: solver_method :{sm} is out of scope; only :PreconditionedConjugateGradient is supported")
+        if sm not in self.SOLVERS:
+            raise ValueError(f"ImplicitFreeSurface: unknown solver_method {solver_method!r}")
+        rect = isinstance(grid, HRectilinearGrid)
+        if preconditioner is DEFAULT or (isinstance(preconditioner, str) and preconditioner == DEFAULT):
+            if rect:
+                raise ValueError("ImplicitFreeSurface: on a RectilinearGrid the reference's default preconditioner is the FFT solver "
+                                 "(FFTImplicitFreeSurfaceSolver), which is out of scope; pass preconditioner=None")
+            preconditioner = None
+        if preconditioner is not None:
+            name = preconditioner if isinstance(preconditioner, str) else type(preconditioner).__name__
+            if "DiagonallyDominant" in str(name):
+                raise ValueError("ImplicitFreeSurface: DiagonallyDominantInversePreconditioner is out of scope: the reference cannot run "
+                                 "it (iterate! calls precondition! with 8 arguments, its method takes 7: a MethodError)")
+            raise ValueError(f"ImplicitFreeSurface: preconditioner {name!r} is out of scope (the FFT preconditioner included); pass "
+                             "preconditioner=None")
+        whole = grid.whole()
+        self.grid, self.lib = whole, whole.lib
+        self.gravitational_acceleration = float(gravitational_acceleration)
+        self.reltol = min(1e-7, 10 * np.sqrt(np.finfo(float).eps)) if reltol is None else float(reltol)
+        self.abstol = float(abstol)
+        self.maxiter = whole.Nx * whole.global_Ny if maxiter is None else int(maxiter)
+        if not (self.reltol >= 0 and self.abstol >= 0 and np.isfinite(self.reltol) and np.isfinite(self.abstol)):
+            raise ValueError("ImplicitFreeSurface: reltol and abstol must be finite and >= 0")
+        if self.maxiter < 0:
+            raise ValueError("ImplicitFreeSurface: maxiter must be >= 0")
+        self.solver_method, self.preconditioner = "PreconditionedConjugateGradient", None
+        self.h = C.c_void_p()
+        check(self.lib.ocn_ifs_create(whole.h, self.gravitational_acceleration, self.reltol, self.abstol, self.maxiter, C.byref(self.h)),
+              whole.ctx.h)
+        self.fields = {}
+        for q, (name, loc) in enumerate(_IFS_FIELDS):
+            f = HField(whole, loc + (Nothing,), handle=self.lib.ocn_ifs_field(self.h, q))
+            self.fields[name] = f
+            setattr(self, _IFS_ASCII[name], f)
+
+    def _last(self):
+        n, r = C.c_int64(), C.c_double()
+        check(self.lib.ocn_ifs_iterations(self.h, C.byref(n), C.byref(r)), self.grid.ctx.h)
+        return n.value, r.value
+
+    @property
+    def iterations(self):
+        """solver.iteration: the iterations of the last solve"""
+        return self._last()[0]
+
+    @property
+    def residual_norm(self):
+        """‖r‖ at the stop test of the last solve"""
+        return self._last()[1]
+
+    def step(self, u, v, dt):
+        """implicit_free_surface_step! from the velocities u, v of the free surface's grid (fills, ∫ᶻQ, right-hand side, solve, fill of η)"""
+        check(self.lib.ocn_ifs_step(self.h, u.h, v.h, float(dt)), self.grid.ctx.h)
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.lib.ocn_ifs_destroy(self.h)
+                self.h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def ExplicitFreeSurface(*args, **kwargs):
+    """the reference's ExplicitFreeSurface: out of scope"""
+    raise ValueError("ExplicitFreeSurface is out of scope: use SplitExplicitFreeSurface or ImplicitFreeSurface")
+
+
 # ---- second slice: the AB2 step of the hydrostatic model around its tendencies ----------------------------------------------------
 def Field3(grid, lx, ly, lz=Center):
     return HField(grid, (lx, ly, lz))
@@ -445,8 +538,9 @@ SIDES = ("west", "east", "south", "north", "bottom", "top")     # OCN_WEST .. OC
 
 
 class HydrostaticState:
-    """the fields of a HydrostaticFreeSurfaceModel{SplitExplicitFreeSurface} the step after the tendencies touches: u, v, w, the
-    tracers, G^n and G^- of the prognostic fields, pHY' and the free surface (hydrostatic_free_surface_model.jl:92-211)"""
+    """the fields of a HydrostaticFreeSurfaceModel the step after the tendencies touches: u, v, w, the tracers, G^n and G^- of the
+    prognostic fields, pHY' and the free surface (hydrostatic_free_surface_model.jl:92-211): a SplitExplicitFreeSurface (the default,
+    built from substeps and gravitational_acceleration) or the ImplicitFreeSurface passed as free_surface"""
 
     def __init__(self, grid, tracers=("T", "S"), buoyancy=None, substeps=20, gravitational_acceleration=g_Earth, free_surface=None,
                  momentum_advection="VectorInvariantEnstrophyConserving", coriolis=None, tracer_advection="CenteredSecondOrder",
@@ -463,10 +557,14 @@ class HydrostaticState:
         self.buoyancy = buoyancy
         # on latitude bands the free surface is replicated (it lives on the whole grid, every rank sub-cycles all of it) or, with
         # barotropic_overlap = W > 0, banded: it lives on the band extended by W rows and refreshes them every W substeps
+        implicit = isinstance(free_surface, ImplicitFreeSurface)
+        if implicit and barotropic_overlap:
+            raise ValueError("the banded free surface (barotropic_overlap > 0) is a split-explicit one: an ImplicitFreeSurface is "
+                             "replicated on every band")
         fsgrid = grid.whole() if not (grid.partition and barotropic_overlap) else grid.extended(barotropic_overlap)
         self.free_surface = free_surface or SplitExplicitFreeSurface(fsgrid, gravitational_acceleration, substeps)
         d = L.HydroDesc()
-        d.free_surface = self.free_surface.h
+        d.free_surface = None if implicit else self.free_surface.h
         d.u, d.v, d.w, d.pHY = self.u.h, self.v.h, self.w.h, self.pHY.h
         tl = list(self.tracers.values())
         d.ntracers = len(tl)
@@ -479,7 +577,10 @@ class HydrostaticState:
         d.S_index = tl.index(S) if S is not None else -1
         d.gravitational_acceleration, d.thermal_expansion, d.haline_contraction = g, al, be
         self.h = C.c_void_p()
-        check(self.lib.ocn_hydro_create(C.byref(d), C.byref(self.h)), grid.ctx.h)
+        if implicit:
+            check(self.lib.ocn_hydro_create_implicit(C.byref(d), self.free_surface.h, C.byref(self.h)), grid.ctx.h)
+        else:
+            check(self.lib.ocn_hydro_create(C.byref(d), C.byref(self.h)), grid.ctx.h)
         self.set_physics(momentum_advection, coriolis, tracer_advection)
         self.set_closure(closure)
         self.set_boundary_conditions(boundary_conditions)

@@ -448,6 +448,26 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h);
 /* time_step!(model, dt; euler) (TimeSteppers/quasi_adams_bashforth_2.jl:70-104): chi = -1/2 and G^- = 0 when euler, else 0.1 */
 int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler);
 
+/* ---- ImplicitFreeSurface(solver_method = :PreconditionedConjugateGradient, preconditioner = nothing) ----------------------------
+ * (Models/HydrostaticFreeSurfaceModels/implicit_free_surface.jl, pcg_implicit_free_surface_solver.jl, Solvers/
+ * preconditioned_conjugate_gradient_solver.jl).  Lives on the whole grid (a model on latitude bands all-gathers ∫ᶻQ and every rank
+ * solves the whole 2-D problem).  reltol, abstol >= 0, maxiter >= 0 (the reference's defaults: 1e-7, 0, Nx Ny).  ∫ᶻA is computed once
+ * at creation (its halos those of the grid, not the reference's (3, 3, 1): the cells the operator reads agree). */
+typedef struct ocn_ifs ocn_ifs;
+int ocn_ifs_create(ocn_hgrid* g, double gravitational_acceleration, double reltol, double abstol, int64_t maxiter, ocn_ifs** out);
+void ocn_ifs_destroy(ocn_ifs* s);
+/* which: 0 η (Center, Center), 1 ∫ᶻQ.u (Face, Center), 2 ∫ᶻQ.v (Center, Face), 3 ∫ᶻ_Axᶠᶜᶜ, 4 ∫ᶻ_Ayᶜᶠᶜ, 5 the right-hand side; owned */
+ocn_hfield* ocn_ifs_field(ocn_ifs* s, int which);
+/* the iterations of the last solve (solver.iteration) and ‖r‖ at its stop test */
+int ocn_ifs_iterations(const ocn_ifs* s, int64_t* iterations, double* residual_norm);
+/* implicit_free_surface_step! (implicit_free_surface.jl:125-160) from the velocities u, v of the free surface's grid: fills of u and v,
+ * ∫ᶻQ, the right-hand side, the PCG solve for η (initial guess: η), the fill of η.  OCN_ESTATE when ‖r‖ stops being finite. */
+int ocn_ifs_step(ocn_ifs* s, ocn_hfield* u, ocn_hfield* v, double dt);
+/* the model of ocn_hydro_create on the implicit free surface (desc->free_surface must be NULL): ab2_step! ends with
+ * implicit_free_surface_step!, the correction is u -= g Δt ∂x η, v -= g Δt ∂y η; every other entry point works as on the split-explicit
+ * free surface */
+int ocn_hydro_create_implicit(const ocn_hydro_desc* desc, ocn_ifs* free_surface, ocn_hydro** out);
+
 /* ---- measurement helpers (bench.py) -------------------------------------------------------------- */
 /* average device time [ms] of the `n` most recent launches of the named phase, measured with HIP
  * events on the context stream when profiling is enabled */

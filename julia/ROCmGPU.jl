@@ -217,6 +217,13 @@ kernel_path(model::RM) = (buf = Vector{UInt8}(undef, 256);
 #       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble), fs.sefs, Gⁿ.u, Gⁿ.v, G⁻.u, G⁻.v, Δt, χ))
 #   barotropic_split_explicit_corrector!(u, v, fs, grid) = check(ccall((:ocn_sefs_corrector, libocnhip), Cint,
 #       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), fs.sefs, hfield(u), hfield(v)))
+#   ImplicitFreeSurface(; solver_method = :PreconditionedConjugateGradient, preconditioner = nothing) (implicit_free_surface.jl):
+#   struct ROCmImplicit; grid::Ptr{Cvoid}; ifs::Ptr{Cvoid}; end     # ocn_ifs_create(grid, g, reltol, abstol, maxiter) (1e-7, 0, Nx Ny)
+#   FreeSurface(fs::ImplicitFreeSurface, velocities, grid) on a ROCmGPU grid -> η, ∫ᶻQ, rhs aliased from ocn_ifs_field(ifs, 0:5);
+#       any other solver_method or a preconditioner throws ArgumentError (the library has the unpreconditioned PCG only)
+#   ab2_step_free_surface!(fs::ImplicitFreeSurface, model, Δt, χ, _) = check(ccall((:ocn_ifs_step, libocnhip), Cint,
+#       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble), fs.ifs, hfield(model.velocities.u), hfield(model.velocities.v), Δt))
+#   the model handle: ocn_hydro_create_implicit(desc, fs.ifs, h) with desc.free_surface = C_NULL; solver.iteration = ocn_ifs_iterations
 #
 # Launch-bound models (config 1) are replayed from hipGraphs inside ocn_time_step; ocn_model_graph_replays(handle, n, active)
 # reports it.  The library reports OCN_ABI_VERSION through ocn_abi_version(): __init__ compares it with 5.
