@@ -174,6 +174,8 @@ def load():
         "ocn_hydro_calculate_tendencies": (I, [P]),
         "ocn_hydro_time_step": (I, [P, D, I]),
         "ocn_ifs_create": (I, [P, D, D, D, C.c_int64, C.POINTER(P)]),
+        "ocn_ifs_create_fft": (I, [P, D, C.POINTER(P)]),
+        "ocn_ifs_method": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
         "ocn_ifs_destroy": (None, [P]),
         "ocn_ifs_field": (P, [P, I]),
         "ocn_ifs_iterations": (I, [P, C.POINTER(C.c_int64), PD]),

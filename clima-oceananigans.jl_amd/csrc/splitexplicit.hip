@@ -1041,6 +1041,7 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 
 // the implicit free surface (ImplicitFreeSurface with the PCG solver)
 #include "hyimplicit.h"
+#include "hyfftfs.h"
 
 // implicit_step! for VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) with constant coefficients
 // (vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121): the tridiagonal coefficients depend on
@@ -1216,6 +1217,12 @@ struct ocn_ifs {
   int64_t iterations = 0;                               // of the last solve
   double rnorm = 0.0;                                   // ‖r‖ at the end of the last solve
   int last_iters = 0;                                   // the first batch of the next solve is sized by it
+  // solver_method = :FastFourierTransform (hyfftfs.h): method 1; Ax, Ay and the PCG's arrays stay null
+  int method = 0;
+  FfsDir fdir[2];                                       // x and y: length, topology, path, radices, the device tables
+  void* ftab[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // tw, ph, lam of x and of y (device)
+  int fcap[2] = {0, 0}, fL[3] = {1, 1, 1};              // LDS capacity per direction; lines per workgroup of the three kernels
+  double* spec = nullptr;                               // Nx x Ny coefficients between the kernels
 };
 
 // ---- the hydrostatic step (second slice) ----------------------------------------------------------------------------------------
@@ -1746,7 +1753,9 @@ static void ifs_vsum_launch(ocn_hfield* Q, long off, const ocn_hfield* u, const 
 }
 // fill_halo_regions!(∫ᶻQ), the right-hand side, solve!(η, ...) and fill_halo_regions!(η) (implicit_free_surface.jl:137-155): the
 // iterations go out in batches, the first sized by the last solve's count, and the host reads the stop flag once per batch
+static int ffs_solve(ocn_ifs* s, double dt);
 static int ifs_solve(ocn_ifs* s, double dt) {
+  if (s->method == 1) return ffs_solve(s, dt);
   ocn_ctx* ctx = s->g->ctx;
   hipStream_t st = ctx->stream;
   hfield_fill(s->Qu);
@@ -1787,6 +1796,32 @@ static int ifs_solve(ocn_ifs* s, double dt) {
     return OCN_ESTATE;
   }
   hfield_fill(s->eta);
+  return OCN_OK;
+}
+// the FFT solver's step: fill_halo_regions!(∫ᶻQ), then rhs + x transform, y transforms around the division, inverse x transform, the
+// fill of η (hyfftfs.h).  m = -1 / (g Lz Δt²) is an argument: nothing depends on Δt but the launches' scalars.
+static int ffs_solve(ocn_ifs* s, double dt) {
+  const ocn_hgrid* g = s->g;
+  hipStream_t st = g->ctx->stream;
+  hfield_fill(s->Qu);
+  hfield_fill(s->Qv);
+  FfsGeo q;
+  q.Nx = g->N[0]; q.Ny = g->N[1]; q.Hx = g->H[0]; q.Hy = g->H[1]; q.Tx = s->eta->T[0];
+  q.su = s->Qu->T[0]; q.sv = s->Qv->T[0];
+  const double Lz = g->L[2], m = -1.0 / (s->grav * Lz * (dt * dt)), norm = 1.0 / ((double)q.Nx * q.Ny);
+  const FfsDir &dx = s->fdir[0], &dy = s->fdir[1];
+  const dim3 blk(FFS_NT, 1, 1), gx((q.Ny + s->fL[0] - 1) / s->fL[0], 1, 1), gy((q.Nx + s->fL[1] - 1) / s->fL[1], 1, 1);
+  const double *eta = s->eta->d, *Qu = s->Qu->d, *Qv = s->Qv->d, *az = g->azcc, *lamx = dx.lam;
+  if (s->fcap[0] == 2048) ocn_launch_sync(k_ffs_x_fwd<2048>, gx, blk, st, q, dx, s->fL[0], eta, Qu, Qv, az, s->rhs->d, s->spec, dt, s->grav * Lz * dt);
+  else ocn_launch_sync(k_ffs_x_fwd<4096>, gx, blk, st, q, dx, s->fL[0], eta, Qu, Qv, az, s->rhs->d, s->spec, dt, s->grav * Lz * dt);
+  if (s->fcap[1] == 2048) ocn_launch_sync(k_ffs_y_solve<2048>, gy, blk, st, dy, s->fL[1], q.Nx, lamx, s->spec, m, norm);
+  else ocn_launch_sync(k_ffs_y_solve<4096>, gy, blk, st, dy, s->fL[1], q.Nx, lamx, s->spec, m, norm);
+  if (s->fcap[0] == 2048) ocn_launch_sync(k_ffs_x_inv<2048>, gx, blk, st, q, dx, s->fL[0], (const double*)s->spec, s->eta->d);
+  else ocn_launch_sync(k_ffs_x_inv<4096>, gx, blk, st, q, dx, s->fL[0], (const double*)s->spec, s->eta->d);
+  const IfsGeo geo = ifs_geo(s);
+  ocn_launch(k_ffs_fill, dim3((geo.Tx * geo.Ty + 255) / 256, 1, 1), dim3(256, 1, 1), st, geo, s->eta->d);
+  s->iterations = 0;
+  s->rnorm = 0.0;
   return OCN_OK;
 }
 // pressure_correct_velocities!(::ImplicitFreeSurfaceHFSM): u -= g Δt ∂x η, v -= g Δt ∂y η over the grid's cells
@@ -3098,6 +3133,128 @@ int ocn_ifs_create(ocn_hgrid* g, double gravitational_acceleration, double relto
   return api_done(ctx, OCN_OK);
 }
 
+/* ---- ImplicitFreeSurface(solver_method = :FastFourierTransform) (hyfftfs.h) -------------------------------------------------------- */
+// the largest power of two <= n (n >= 1)
+static int ffs_pow2floor(int n) {
+  int p = 1;
+  while (2 * p <= n) p *= 2;
+  return p;
+}
+// the tables of one direction, in double precision from extended-precision angles; radices 4 first, then 2, 3, 5
+static int ffs_axis(ocn_ctx* ctx, int N, int bounded, double L, FfsDir* d, void** tab) {
+  d->N = N;
+  d->bounded = bounded;
+  d->nst = 0;
+  int n = N;
+  for (int r : {4, 2, 3, 5})
+    while (n % r == 0 && d->nst < FFS_MAXST) {
+      d->rad[d->nst++] = r;
+      n /= r;
+    }
+  d->fast = n == 1;
+  if (!d->fast) d->nst = 0;
+  const long double pi = 3.141592653589793238462643383279502884L;
+  std::vector<ffs_c> tw(N), ph(N);
+  std::vector<double> lam(N);
+  const double delta = L / N;
+  for (int k = 0; k < N; ++k) {
+    const long double a = 2 * pi * k / N, b = pi * k / (2.0L * N);
+    tw[k] = ffs_c{(double)cosl(a), (double)-sinl(a)};
+    ph[k] = ffs_c{(double)cosl(b), (double)-sinl(b)};
+    const double sn = bounded ? (double)sinl(b) : (double)sinl(pi * k / N);
+    lam[k] = (2 * sn / delta) * (2 * sn / delta);
+  }
+  struct { const void* h; size_t bytes; } up[3] = {{tw.data(), N * sizeof(ffs_c)}, {ph.data(), N * sizeof(ffs_c)}, {lam.data(), N * sizeof(double)}};
+  for (int q = 0; q < 3; ++q) {
+    OCN_HIP_CHECK(ctx, hipMalloc(&tab[q], up[q].bytes));
+    OCN_HIP_CHECK(ctx, hipMemcpy(tab[q], up[q].h, up[q].bytes, hipMemcpyHostToDevice));
+  }
+  d->tw = (const ffs_c*)tab[0];
+  d->ph = (const ffs_c*)tab[1];
+  d->lam = (const double*)tab[2];
+  return OCN_OK;
+}
+
+int ocn_ifs_create_fft(ocn_hgrid* g, double gravitational_acceleration, ocn_ifs** out) {
+  if (!g || !out) return OCN_EINVAL;
+  ocn_ctx* ctx = g->ctx;
+  if (g->kind != HG_RECT) {
+    ocn_set_error(ctx, "ocn_ifs_create_fft: the FFT-based implicit free surface solver requires horizontally-regular rectilinear grids");
+    return OCN_EINVAL;
+  }
+  if (g->slab || g->overlap > 0) {
+    ocn_set_error(ctx, "ocn_ifs_create_fft: the implicit free surface lives on the whole grid (every rank solves all of it); pass the unpartitioned grid");
+    return OCN_EINVAL;
+  }
+  if (!(gravitational_acceleration > 0) || !std::isfinite(gravitational_acceleration)) {
+    ocn_set_error(ctx, "ocn_ifs_create_fft: the gravitational acceleration must be finite and > 0");
+    return OCN_EINVAL;
+  }
+  for (int d = 0; d < 2; ++d)
+    if (g->N[d] > FFS_NMAX) {
+      ocn_set_error(ctx, "ocn_ifs_create_fft: %d points in %c: a line and its ping-pong buffer must fit in LDS, %d points per direction at most",
+                    g->N[d], d ? 'y' : 'x', FFS_NMAX);
+      return OCN_EINVAL;
+    }
+  if (g->H[0] < 1 || g->H[1] < 1) {
+    ocn_set_error(ctx, "ocn_ifs_create_fft: needs one halo cell in x and y");
+    return OCN_EINVAL;
+  }
+  for (int d = 0; d < 2; ++d)
+    if (g->topo[d] == OCN_PERIODIC && g->N[d] < g->H[d]) {
+      ocn_set_error(ctx, "ocn_ifs_create_fft: a Periodic direction needs at least as many cells as halo cells");
+      return OCN_EINVAL;
+    }
+  ocn_ifs* s = new ocn_ifs;
+  s->g = g;
+  g->refs += 1;
+  s->method = 1;
+  s->grav = gravitational_acceleration;
+  s->reltol = s->abstol = 0.0;
+  s->maxiter = 0;
+  s->eta = s->Qu = s->Qv = s->Ax = s->Ay = s->rhs = nullptr;
+  struct { ocn_hfield** f; int lx, ly; } tab[] = {{&s->eta, OCN_CENTER, OCN_CENTER}, {&s->Qu, OCN_FACE, OCN_CENTER}, {&s->Qv, OCN_CENTER, OCN_FACE},
+                                                  {&s->rhs, OCN_CENTER, OCN_CENTER}};
+  for (auto& t : tab)
+    if (int rc = hfield_new(g, t.lx, t.ly, OCN_NOTHING, t.f)) {
+      ocn_ifs_destroy(s);
+      return rc;
+    }
+  for (int d = 0; d < 2; ++d) {
+    if (int rc = ffs_axis(ctx, g->N[d], g->topo[d] != OCN_PERIODIC, g->L[d], &s->fdir[d], &s->ftab[3 * d])) {
+      ocn_ifs_destroy(s);
+      return rc;
+    }
+    s->fcap[d] = g->N[d] <= 2048 ? 2048 : 4096;
+  }
+  if (hipMalloc((void**)&s->spec, (size_t)g->N[0] * g->N[1] * sizeof(double)) != hipSuccess) {
+    ocn_ifs_destroy(s);
+    ocn_set_error(ctx, "ocn_ifs_create_fft: allocation failed");
+    return OCN_ENOMEM;
+  }
+  // lines per workgroup: rows share a workgroup while a row leaves threads idle (four points per thread); the y kernel takes up to
+  // eight adjacent coefficients so that its loads are 64-byte runs along x
+  const int rows = s->fcap[0] / g->N[0], want = 1024 / g->N[0] > 1 ? 1024 / g->N[0] : 1;
+  s->fL[0] = ffs_pow2floor(rows < want ? rows : want);
+  if (s->fL[0] > 64) s->fL[0] = 64;
+  const int cols = s->fcap[1] / g->N[1];
+  s->fL[1] = ffs_pow2floor(cols < 8 ? cols : 8);
+  if (getenv("OCNHIP_DEBUG"))
+    fprintf(stderr, "[ocnhip] FFT implicit free surface %d x %d: x %s %s (%d stages, %d rows per workgroup), y %s %s (%d stages, %d columns per workgroup)\n",
+            g->N[0], g->N[1], s->fdir[0].bounded ? "Bounded" : "Periodic", s->fdir[0].fast ? "fast" : "direct", s->fdir[0].nst, s->fL[0],
+            s->fdir[1].bounded ? "Bounded" : "Periodic", s->fdir[1].fast ? "fast" : "direct", s->fdir[1].nst, s->fL[1]);
+  *out = s;
+  return api_done(ctx, OCN_OK);
+}
+
+int ocn_ifs_method(const ocn_ifs* s, int* method, int* x_path, int* y_path) {
+  if (!s) return OCN_EINVAL;
+  if (method) *method = s->method;
+  if (x_path) *x_path = s->method == 1 ? !s->fdir[0].fast : 0;
+  if (y_path) *y_path = s->method == 1 ? !s->fdir[1].fast : 0;
+  return OCN_OK;
+}
+
 void ocn_ifs_destroy(ocn_ifs* s) {
   if (!s) return;
   hipStreamSynchronize(s->g->ctx->stream);
@@ -3109,6 +3266,8 @@ void ocn_ifs_destroy(ocn_ifs* s) {
       hgrid_release(g);          // the reference hfield_new took
     }
   for (void* a : {(void*)s->r, (void*)s->q, (void*)s->p0, (void*)s->p1, (void*)s->prr, (void*)s->ppq, (void*)s->st}) hipFree(a);
+  for (void* a : s->ftab) hipFree(a);
+  hipFree(s->spec);
   delete s->hst;
   delete s;
   hgrid_release(g);

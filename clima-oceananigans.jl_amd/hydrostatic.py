@@ -282,31 +282,48 @@ DEFAULT = "default"        # ImplicitFreeSurface(preconditioner=DEFAULT): the re
 
 
 class ImplicitFreeSurface:
-    """ImplicitFreeSurface(grid; solver_method = :PreconditionedConjugateGradient, gravitational_acceleration, reltol, abstol, maxiter,
-    preconditioner = nothing) (Models/HydrostaticFreeSurfaceModels/implicit_free_surface.jl, pcg_implicit_free_surface_solver.jl): the
-    free surface solved for implicitly by an unpreconditioned conjugate gradient.  None takes the reference's default: reltol =
-    min(1e-7, 10 sqrt(eps)) = 1e-7, maxiter = Nx Ny.  On a latitude band the free surface lives on the whole grid.  The reference's
-    default solver_method, the other solvers and every preconditioner are refused with a ValueError; on an HRectilinearGrid (where the
-    reference's default preconditioner is its FFT solver) pass preconditioner=None."""
+    """ImplicitFreeSurface(grid; solver_method, gravitational_acceleration, reltol, abstol, maxiter, preconditioner)
+    (Models/HydrostaticFreeSurfaceModels/implicit_free_surface.jl).  Two of the reference's solvers:
 
-    SOLVERS = ("PreconditionedConjugateGradient",)
+    * ``"PreconditionedConjugateGradient"`` (pcg_implicit_free_surface_solver.jl; this mirror's default): an unpreconditioned conjugate
+      gradient, on either grid.  None takes the reference's default: reltol = min(1e-7, 10 sqrt(eps)) = 1e-7, maxiter = Nx Ny.  Every
+      preconditioner is refused with a ValueError; on an HRectilinearGrid (where the reference's default preconditioner is its FFT
+      solver) pass preconditioner=None.  The FFT preconditioner stays out on purpose: without immersed bathymetry it is the exact
+      inverse, and the preconditioned iteration would be the direct solve below plus one wasted iteration.
+    * ``"FastFourierTransform"`` (fft_based_implicit_free_surface_solver.jl), and ``"Default"`` on an HRectilinearGrid, which selects it
+      as the reference does: a direct solve by an eigenfunction expansion in x and y.  Needs an HRectilinearGrid (regular x and y, flat
+      bottom) with at most 4096 points per direction.  reltol, abstol, maxiter and preconditioner are accepted and ignored, as the
+      reference ignores its settings; ``iterations`` is 0.
+
+    On a latitude band the free surface lives on the whole grid.  On a LatitudeLongitudeGrid every method but the PCG is refused (the
+    reference refuses the FFT solver there, and its default there is the heptadiagonal solver)."""
+
+    SOLVERS = ("PreconditionedConjugateGradient", "FastFourierTransform")
 
     def __init__(self, grid, gravitational_acceleration=g_Earth, solver_method="PreconditionedConjugateGradient", reltol=None, abstol=0.0,
                  maxiter=None, preconditioner=DEFAULT):
         sm = str(solver_method).lstrip(":")
+        rect = isinstance(grid, HRectilinearGrid)
         if sm == "Default":
-            raise ValueError("ImplicitFreeSurface: solver_method :Default is out of scope (it selects :HeptadiagonalIterativeSolver on a "
-                             "LatitudeLongitudeGrid and :FastFourierTransform on a regular RectilinearGrid); pass "
-                             "solver_method='PreconditionedConjugateGradient'")
-        if sm in ("HeptadiagonalIterativeSolver", "FastFourierTransform", "Multigrid"):
-            raise ValueError(f"ImplicitFreeSurface: solver_method :{sm} is out of scope; only :PreconditionedConjugateGradient is supported")
+            if not rect:
+                raise ValueError("ImplicitFreeSurface: solver_method :Default selects :HeptadiagonalIterativeSolver on a "
+                                 "LatitudeLongitudeGrid, which is out of scope; pass solver_method='PreconditionedConjugateGradient'")
+            sm = "FastFourierTransform"
+        if sm in ("HeptadiagonalIterativeSolver", "Multigrid"):
+            raise ValueError(f"ImplicitFreeSurface: solver_method :{sm} is out of scope; :PreconditionedConjugateGradient and, on an "
+                             "HRectilinearGrid, :FastFourierTransform are supported")
         if sm not in self.SOLVERS:
             raise ValueError(f"ImplicitFreeSurface: unknown solver_method {solver_method!r}")
-        rect = isinstance(grid, HRectilinearGrid)
+        if sm == "FastFourierTransform":
+            if not rect:
+                raise ValueError("ImplicitFreeSurface: FFTImplicitFreeSurfaceSolver requires horizontally-regular rectilinear grids")
+            self._create(grid, gravitational_acceleration, sm, 0.0, 0.0, 0)
+            return
         if preconditioner is DEFAULT or (isinstance(preconditioner, str) and preconditioner == DEFAULT):
             if rect:
                 raise ValueError("ImplicitFreeSurface: on a RectilinearGrid the reference's default preconditioner is the FFT solver "
-                                 "(FFTImplicitFreeSurfaceSolver), which is out of scope; pass preconditioner=None")
+                                 "(FFTImplicitFreeSurfaceSolver), which is out of scope as a preconditioner; pass preconditioner=None, or "
+                                 "solver_method='FastFourierTransform' for the direct solve")
             preconditioner = None
         if preconditioner is not None:
             name = preconditioner if isinstance(preconditioner, str) else type(preconditioner).__name__
@@ -316,24 +333,40 @@ class ImplicitFreeSurface:
             raise ValueError(f"ImplicitFreeSurface: preconditioner {name!r} is out of scope (the FFT preconditioner included); pass "
                              "preconditioner=None")
         whole = grid.whole()
+        reltol = min(1e-7, 10 * np.sqrt(np.finfo(float).eps)) if reltol is None else float(reltol)
+        maxiter = whole.Nx * whole.global_Ny if maxiter is None else int(maxiter)
+        if not (reltol >= 0 and float(abstol) >= 0 and np.isfinite(reltol) and np.isfinite(float(abstol))):
+            raise ValueError("ImplicitFreeSurface: reltol and abstol must be finite and >= 0")
+        if maxiter < 0:
+            raise ValueError("ImplicitFreeSurface: maxiter must be >= 0")
+        self._create(grid, gravitational_acceleration, sm, reltol, float(abstol), maxiter)
+
+    def _create(self, grid, gravitational_acceleration, solver_method, reltol, abstol, maxiter):
+        whole = grid.whole()
         self.grid, self.lib = whole, whole.lib
         self.gravitational_acceleration = float(gravitational_acceleration)
-        self.reltol = min(1e-7, 10 * np.sqrt(np.finfo(float).eps)) if reltol is None else float(reltol)
-        self.abstol = float(abstol)
-        self.maxiter = whole.Nx * whole.global_Ny if maxiter is None else int(maxiter)
-        if not (self.reltol >= 0 and self.abstol >= 0 and np.isfinite(self.reltol) and np.isfinite(self.abstol)):
-            raise ValueError("ImplicitFreeSurface: reltol and abstol must be finite and >= 0")
-        if self.maxiter < 0:
-            raise ValueError("ImplicitFreeSurface: maxiter must be >= 0")
-        self.solver_method, self.preconditioner = "PreconditionedConjugateGradient", None
+        self.reltol, self.abstol, self.maxiter = reltol, abstol, maxiter
+        self.solver_method, self.preconditioner = solver_method, None
         self.h = C.c_void_p()
-        check(self.lib.ocn_ifs_create(whole.h, self.gravitational_acceleration, self.reltol, self.abstol, self.maxiter, C.byref(self.h)),
-              whole.ctx.h)
+        if solver_method == "FastFourierTransform":
+            check(self.lib.ocn_ifs_create_fft(whole.h, self.gravitational_acceleration, C.byref(self.h)), whole.ctx.h)
+        else:
+            check(self.lib.ocn_ifs_create(whole.h, self.gravitational_acceleration, reltol, abstol, maxiter, C.byref(self.h)), whole.ctx.h)
         self.fields = {}
         for q, (name, loc) in enumerate(_IFS_FIELDS):
-            f = HField(whole, loc + (Nothing,), handle=self.lib.ocn_ifs_field(self.h, q))
+            handle = self.lib.ocn_ifs_field(self.h, q)
+            if not handle:
+                continue                   # the FFT solver has no ∫ᶻA
+            f = HField(whole, loc + (Nothing,), handle=handle)
             self.fields[name] = f
             setattr(self, _IFS_ASCII[name], f)
+
+    @property
+    def transform_paths(self):
+        """per direction (x, y): "fast" (N = 2^a 3^b 5^c) or "direct"; None for the PCG"""
+        m, px, py = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.ocn_ifs_method(self.h, C.byref(m), C.byref(px), C.byref(py)), self.grid.ctx.h)
+        return None if m.value == 0 else tuple("direct" if p.value else "fast" for p in (px, py))
 
     def _last(self):
         n, r = C.c_int64(), C.c_double()

@@ -467,6 +467,17 @@ int ocn_ifs_step(ocn_ifs* s, ocn_hfield* u, ocn_hfield* v, double dt);
  * implicit_free_surface_step!, the correction is u -= g Δt ∂x η, v -= g Δt ∂y η; every other entry point works as on the split-explicit
  * free surface */
 int ocn_hydro_create_implicit(const ocn_hydro_desc* desc, ocn_ifs* free_surface, ocn_hydro** out);
+/* ImplicitFreeSurface(solver_method = :FastFourierTransform) (fft_based_implicit_free_surface_solver.jl, Solvers/
+ * fft_based_poisson_solver.jl): the same handle type, solved directly by an eigenfunction expansion in x and y,
+ * (∇² - 1 / (g Lz Δt²)) η = (δx ∫ᶻQ.u + δy ∫ᶻQ.v - Az η / Δt) / (g Lz Δt Az).  Needs a rectilinear grid (OCN_EINVAL on a
+ * latitude-longitude grid: the reference's ArgumentError), a flat bottom, Periodic or Bounded x and y, and at most 4096 points per
+ * direction (a line must fit in LDS; OCN_EINVAL otherwise).  Lengths 2^a 3^b 5^c take a fast transform, every other length a direct
+ * O(N²) one.  Every entry point above works on the handle; ocn_ifs_field returns NULL for 3 and 4 (this solver has no ∫ᶻA), and 5 is
+ * this solver's right-hand side, which -- unlike the reference's, whose storage the solve overwrites -- is still there after the
+ * step; ocn_ifs_iterations reports 0 iterations and a zero residual. */
+int ocn_ifs_create_fft(ocn_hgrid* g, double gravitational_acceleration, ocn_ifs** out);
+/* method: 0 PCG, 1 FFT; x_path, y_path: 0 the fast transform, 1 the direct one (0 for a PCG handle); any pointer may be NULL */
+int ocn_ifs_method(const ocn_ifs* s, int* method, int* x_path, int* y_path);
 
 /* ---- measurement helpers (bench.py) -------------------------------------------------------------- */
 /* average device time [ms] of the `n` most recent launches of the named phase, measured with HIP

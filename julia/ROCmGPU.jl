@@ -223,6 +223,9 @@ kernel_path(model::RM) = (buf = Vector{UInt8}(undef, 256);
 #       any other solver_method or a preconditioner throws ArgumentError (the library has the unpreconditioned PCG only)
 #   ab2_step_free_surface!(fs::ImplicitFreeSurface, model, Δt, χ, _) = check(ccall((:ocn_ifs_step, libocnhip), Cint,
 #       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble), fs.ifs, hfield(model.velocities.u), hfield(model.velocities.v), Δt))
+#   solver_method = :FastFourierTransform, or :Default on a regular RectilinearGrid: fs.ifs from ocn_ifs_create_fft(grid, g) instead (flat
+#       bottom, <= 4096 points per direction; settings ignored as the reference ignores them; ocn_ifs_field(ifs, 3:4) are C_NULL: no ∫ᶻA;
+#       ocn_ifs_method(ifs, method, x_path, y_path) tells 0 PCG / 1 FFT and 0 fast / 1 direct transform per direction)
 #   the model handle: ocn_hydro_create_implicit(desc, fs.ifs, h) with desc.free_surface = C_NULL; solver.iteration = ocn_ifs_iterations
 #
 # Launch-bound models (config 1) are replayed from hipGraphs inside ocn_time_step; ocn_model_graph_replays(handle, n, active)
