@@ -87,6 +87,10 @@ __device__ __forceinline__ double ocn_shfl_xor16(double x) {
   return b.d;
 }
 #define OCN_WAVE 64
+// Cache policy of streams a kernel touches ONCE (the `nt` modifier of global_load / global_store): the line is not worth an
+// L2 slot that data with a second use could keep (k_tend4's slab rows).  Same addressing forms as the plain access.
+#define OCN_LD_NT(p) __builtin_nontemporal_load(p)
+#define OCN_ST_NT(p, v) __builtin_nontemporal_store((v), (p))
 // a value that is the same in every lane of the wave, moved to a scalar register: branches on it are scalar branches
 // (s_setprio and the LDS-DMA base in M0 are scalar state -- behind a "divergent" branch they would execute regardless of EXEC)
 #define OCN_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
@@ -186,6 +190,8 @@ static inline void __syncthreads() { g_emu_barrier.wait(); }
 // wave-level primitives, emulated with one OS thread per GPU thread (every thread of the block must make the call)
 #define OCN_WAVE 64
 #define OCN_UNIFORM(x) (x)
+#define OCN_LD_NT(p) (*(p))                /* cache policies mean nothing on the host */
+#define OCN_ST_NT(p, v) ((void)(*(p) = (v)))
 static inline void ocn_glds16(const void* src_lane, void* dst_wave_base, int lane) {
   memcpy((char*)dst_wave_base + 16 * lane, src_lane, 16);
 }

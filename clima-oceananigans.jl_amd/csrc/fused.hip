@@ -71,6 +71,19 @@ OCN_DEVFN void prio_mid(int code, int sty, int BY) {
 }
 
 OCN_DEVFN void sto(double* base, unsigned boff, double v) { *(double*)((char*)base + boff) = v; }
+// the same accesses for streams touched once per launch (NT: non-temporal, see compat.h); same base + 32-bit offset form
+template <bool NT>
+OCN_DEVFN double ldo_once(const double* base, unsigned boff) {
+  const double* p = (const double*)((const char*)base + boff);
+  if (NT) return OCN_LD_NT(p);
+  return *p;
+}
+template <bool NT>
+OCN_DEVFN void sto_once(double* base, unsigned boff, double v) {
+  double* p = (double*)((char*)base + boff);
+  if (NT) OCN_ST_NT(p, v);
+  else *p = v;
+}
 
 // ---- k_tend4: tendencies of u, v, w + time-stepper update, ONE barrier per level --------------------------------------
 // A workgroup owns BY-1 output rows (+ one ghost row of threads that only produces the south-face fluxes of the row above
@@ -100,6 +113,14 @@ OCN_DEVFN void sto(double* base, unsigned boff, double v) { *(double*)((char*)ba
 //     them the youngest wave of each SIMD (the ghost row) starves and everybody waits for it.
 // Measured at 256^3 (MI355X, profiles/r02_*): 0.739 -> 0.551 ms together with the leaner WENO algebra of stencils.h.
 //
+// Cache policy (NT): a level of u, v, w is touched several times -- by the z-window load two levels before its slab DMA and by
+// the three y-tiles that need each row, which march two levels apart -- while per level-step the 32 workgroups of an XCD also
+// push about 2.4 MB of data through its 4 MiB L2 that nobody reads again: the three G^- loads and the six G^n / U* stores.
+// With those nine streams non-temporal the reusable rows survive longer: L2 hit rate 0.37 -> 0.47, FETCH_SIZE -20 %, kernel
+// 0.539 -> 0.521 ms, and k_xfft_rhs, the next reader of U*, 0.133 -> 0.121 ms (profiles/step_locality_*).  The stores carry
+// the gain; the loads alone measure nothing, both together 1 % more than the stores alone.  The slab DMA and the z-window
+// loads keep the default policy: they are the data with a second use.  NT = false (OCNHIP_LOCALITY=0): plain accesses.
+//
 // ScalarDiffusivity (VISC; closure_kernel_operators.jl:22-41 with constant nu): div(2 nu Sigma)_i = nu (lap u_i + d_i div U),
 // exactly (centred differences commute on a uniform grid).  Both parts are face fluxes at the very places of the advective
 // ones: -nu d(u_i)/dn through every face, plus -nu div U through the centre-located face of the normal component.
@@ -107,7 +128,7 @@ OCN_DEVFN void sto(double* base, unsigned boff, double v) { *(double*)((char*)ba
 // boundary buffer (topologically_conditional_interpolation.jl:46-79).  REST: G^n arrives holding everything but advection
 // (closure, Coriolis, pressure gradient, boundary fluxes from the general kernels) and leaves as the full tendency;
 // walls in x / y are runtime flags of the REST variants (the same fallbacks on the x / y stencils).
-template <int ADV, int BX, int BY, bool XT, int DMA, bool VISC, bool ZB, bool REST>
+template <int ADV, int BX, int BY, bool XT, int DMA, bool VISC, bool ZB, bool REST, bool NT>
 __global__ void __launch_bounds__(BX* BY) k_tend4(GridDev g, FusedArgs a) {
   constexpr int T = BX * BY, NR = BY + 5, SX = BX + 6;
   constexpr int WV = BX < OCN_WAVE ? BX : OCN_WAVE;   // lanes of a wave that lie in one row
@@ -342,7 +363,7 @@ __global__ void __launch_bounds__(BX* BY) k_tend4(GridDev g, FusedArgs a) {
         rs2 = ldo(a.gnw, cm1);
       }
       const unsigned cgm = a.use_m ? cm1 : a.org;     // without G^- (Euler start, first RK3 stage): one cached element
-      double gm0 = ldo(a.gmu, cgm), gm1 = ldo(a.gmv, cgm), gm2 = ldo(a.gmw, cgm);
+      double gm0 = ldo_once<NT>(a.gmu, cgm), gm1 = ldo_once<NT>(a.gmv, cgm), gm2 = ldo_once<NT>(a.gmw, cgm);
       znu = ldo(a.u, cnx);
       znv = ldo(a.v, cnx);
       znw = ldo(a.w, cnx);
@@ -387,12 +408,12 @@ __global__ void __launch_bounds__(BX* BY) k_tend4(GridDev g, FusedArgs a) {
         iw = a.dt * a.cn * Gw;
       }
       if (upd) {                                      // all six stores together, after the last use of a loaded value
-        sto(a.gnu, cm1, Gu);
-        sto(a.gnv, cm1, Gv);
-        sto(a.gnw, cm1, Gw);
-        sto(a.us, cm1, zu[2] + iu);
-        sto(a.vs, cm1, zv[2] + iv);
-        sto(a.ws, cm1, zw[2] + iw);
+        sto_once<NT>(a.gnu, cm1, Gu);
+        sto_once<NT>(a.gnv, cm1, Gv);
+        sto_once<NT>(a.gnw, cm1, Gw);
+        sto_once<NT>(a.us, cm1, zu[2] + iu);
+        sto_once<NT>(a.vs, cm1, zv[2] + iv);
+        sto_once<NT>(a.ws, cm1, zw[2] + iw);
       }
       bu = Fwu;
       bv = Fwv;
@@ -1038,6 +1059,7 @@ struct FusedShape {
 //   OCNHIP_NO_TRACER3=1   column tracer kernel instead of the tiled one (tests)
 //   OCNHIP_PRIO=code      wave-priority code (see prio_start; 0 = hardware default)
 //   OCNHIP_NO_GRAPH=1     general path: issue every launch of a step from the host instead of replaying a hipGraph
+//   OCNHIP_LOCALITY=0     k_tend4 with the default cache policy on every stream (tests, same-build A/B; see the kernel's note)
 void fused_read_knobs(ocn_model* m) {
   auto env = [](const char* n, int def) { const char* e = getenv(n); return e ? atoi(e) : def; };
   m->knob_fused_xt = env("OCNHIP_FUSED_XT", 0);
@@ -1050,6 +1072,7 @@ void fused_read_knobs(ocn_model* m) {
   // default 0x20FF: every row at priority 3 until the middle of its flux stage, then only the last output row keeps 2
   // (256^3: 0.575 ms against 0.590 with the hardware's age order; ten codes tried, all within 0.575 - 0.613)
   { const char* e = getenv("OCNHIP_PRIO"); m->knob_prio = e ? (int)strtol(e, nullptr, 0) : 0x20FF; }
+  { const char* e = getenv("OCNHIP_LOCALITY"); m->knob_locality = e ? atoi(e) : 1; }
 }
 
 static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
@@ -1113,10 +1136,13 @@ static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
 }
 
 // launch one of the instantiations: VISCV / ZBV / RESTV are compile-time constants at the call site
+#define FUSED_T4N(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV, NTV)                                                             \
+  { if (f.dma == 2 && !XTV) ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, XTV ? 1 : 2, VISCV, ZBV, RESTV, NTV>, f.grd, f.blk, s, m->gd, a); \
+    else if (f.dma) ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, 1, VISCV, ZBV, RESTV, NTV>, f.grd, f.blk, s, m->gd, a);  \
+    else ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, 0, VISCV, ZBV, RESTV, NTV>, f.grd, f.blk, s, m->gd, a); }
 #define FUSED_T4(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV)                                                                   \
-  { if (f.dma == 2 && !XTV) ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, XTV ? 1 : 2, VISCV, ZBV, RESTV>, f.grd, f.blk, s, m->gd, a); \
-    else if (f.dma) ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, 1, VISCV, ZBV, RESTV>, f.grd, f.blk, s, m->gd, a);       \
-    else ocn_launch_sync(k_tend4<ADVV, BXV, BYV, XTV, 0, VISCV, ZBV, RESTV>, f.grd, f.blk, s, m->gd, a); }
+  { if (m->knob_locality) FUSED_T4N(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV, true)                           \
+    else FUSED_T4N(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV, false) }
 #ifdef OCN_HOST_EMU
 #define FUSED_EMU16(ADVV, VISCV, ZBV, RESTV)                                                                               \
   if (f.bx == 16 && f.small) FUSED_T4(ADVV, 16, 4, true, VISCV, ZBV, RESTV)                                                \
