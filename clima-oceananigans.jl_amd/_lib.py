@@ -46,6 +46,10 @@ class ModelDesc(C.Structure):
                 ("bcs", (BC * 6) * (3 + MAX_TRACERS)), ("nu_bcs", BC * 6), ("kappa_bcs", (BC * 6) * MAX_TRACERS)]
 
 
+class SmagorinskyLillyDesc(C.Structure):
+    _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("Pr", C.c_double * MAX_TRACERS)]
+
+
 class HydroDesc(C.Structure):
     _fields_ = [("free_surface", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("w", C.c_void_p), ("pHY", C.c_void_p),
                 ("ntracers", C.c_int32), ("tracers", C.POINTER(C.c_void_p)), ("Gn", C.POINTER(C.c_void_p)), ("Gm", C.POINTER(C.c_void_p)),
@@ -97,6 +101,7 @@ def load():
         "ocn_grid_create": (I, [P, C.POINTER(GridDesc), C.POINTER(P)]),
         "ocn_grid_destroy": (None, [P]),
         "ocn_model_create": (I, [P, C.POINTER(ModelDesc), C.POINTER(P)]),
+        "ocn_model_create_smagorinsky_lilly": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.POINTER(P)]),
         "ocn_model_destroy": (None, [P]),
         "ocn_model_halo": (I, [P, C.POINTER(C.c_int32 * 3)]),
         "ocn_model_path": (I, [P, C.c_char_p, C.c_size_t]),

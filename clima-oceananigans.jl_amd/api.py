@@ -66,6 +66,43 @@ class AnisotropicMinimumDissipation:
         self.Cb = Cb
 
 
+class SmagorinskyLilly:
+    """``SmagorinskyLilly(time_discretization=ExplicitTimeDiscretization(); C=0.16, Cb=1.0, Pr=1.0)``
+    (smagorinsky_lilly.jl:68-69).  ``Pr``: a number or ``{tracer: number}``; kappa_e of a tracer is ``nu_e / Pr``."""
+
+    def __init__(self, C=0.16, Cb=1.0, Pr=1.0, time_discretization="Explicit"):
+        if time_discretization not in ("Explicit", "ExplicitTimeDiscretization"):
+            raise ValueError(f"SmagorinskyLilly(time_discretization={time_discretization!r}): the nonhydrostatic path has no "
+                             "implicit solver, only the Explicit time discretization is supported")
+        for n, val in [("C", C), ("Cb", Cb)] + ([(f"Pr[{k}]", x) for k, x in Pr.items()] if isinstance(Pr, dict) else [("Pr", Pr)]):
+            if not np.isfinite(val):
+                raise ValueError(f"SmagorinskyLilly: {n} = {val} is not finite")
+            if n.startswith("Pr") and val == 0:
+                raise ValueError(f"SmagorinskyLilly: {n} is zero (kappa_e = nu_e / Pr)")
+        self.C, self.Cb, self.Pr = float(C), float(Cb), Pr
+
+    def Pr_of(self, name):
+        return float(self.Pr[name] if isinstance(self.Pr, dict) else self.Pr)
+
+
+def _split_closure(closure):
+    """closure -> (closure of ocn_model_desc, SmagorinskyLilly or None).  Tuples: only the pairing of the reference's ocean-LES
+    regression, (SmagorinskyLilly, ScalarDiffusivity) in either order, whose flux divergences add."""
+    if not isinstance(closure, (tuple, list)):
+        return (None, closure) if isinstance(closure, SmagorinskyLilly) else (closure, None)
+    if len(closure) != 2:
+        raise ValueError(f"closure tuple of length {len(closure)}: only (SmagorinskyLilly, ScalarDiffusivity) is supported")
+    smag = [c for c in closure if isinstance(c, SmagorinskyLilly)]
+    scal = [c for c in closure if isinstance(c, ScalarDiffusivity)]
+    if len(smag) == 2:
+        raise ValueError("closure tuple with two SmagorinskyLilly: only (SmagorinskyLilly, ScalarDiffusivity) is supported")
+    if len(smag) != 1 or len(scal) != 1:
+        other = [type(c).__name__ for c in closure if not isinstance(c, (SmagorinskyLilly, ScalarDiffusivity))]
+        raise ValueError(f"closure tuple with {', '.join(other) or 'two ScalarDiffusivity'}: only (SmagorinskyLilly, "
+                         "ScalarDiffusivity) is supported")
+    return scal[0], smag[0]
+
+
 class FPlane:
     def __init__(self, f):
         self.f = float(f)
@@ -324,6 +361,9 @@ class NonhydrostaticModel:
             raise ValueError(f"unknown timestepper {timestepper}")
         d.chi = float(chi)
         d.n_tracers = len(self.tracer_names)
+        closure, smag = _split_closure(closure)   # smag: SmagorinskyLilly, alone or with the ScalarDiffusivity left in `closure`
+        if smag is not None and Flat in grid.topo:
+            raise ValueError("SmagorinskyLilly on a grid with a Flat direction is outside the path")
         if closure is None:
             d.closure = L.CLOSURE_NONE
         elif isinstance(closure, ScalarDiffusivity):
@@ -372,7 +412,10 @@ class NonhydrostaticModel:
         for fname, sides in (boundary_conditions or {}).items():
             if fname in ("nu_e", "kappa_e"):
                 # boundary_conditions = (; κₑ = (; b = FieldBoundaryConditions(...))) of the reference: the AMD diffusivity fields
-                if not isinstance(closure, AnisotropicMinimumDissipation):
+                if smag is not None and fname == "kappa_e":
+                    raise ValueError("SmagorinskyLilly has no kappa_e field (kappa_e = nu_e / Pr is an operation on nu_e): "
+                                     "boundary conditions for kappa_e cannot apply")
+                if smag is None and not isinstance(closure, AnisotropicMinimumDissipation):
                     raise ValueError(f"boundary conditions for {fname} need a closure with diffusivity fields")
                 if fname == "nu_e":
                     for side, bc in sides.items():
@@ -388,7 +431,16 @@ class NonhydrostaticModel:
                 fill(d.bcs[names.index(fname)], side, bc)
         self.desc = d
         self.h = C.c_void_p()
-        check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
+        if smag is None:
+            check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
+        else:
+            sd = L.SmagorinskyLillyDesc()
+            sd.C, sd.Cb = smag.C, smag.Cb
+            for i, n in enumerate(self.tracer_names):
+                if isinstance(smag.Pr, dict) and n not in smag.Pr:
+                    raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
+                sd.Pr[i] = smag.Pr_of(n)
+            check(self.lib.ocn_model_create_smagorinsky_lilly(grid.h, C.byref(d), C.byref(sd), C.byref(self.h)), self.ctx.h)
         H = (C.c_int32 * 3)()
         check(self.lib.ocn_model_halo(self.h, C.byref(H)), self.ctx.h)
         self.halo = tuple(H)
@@ -402,6 +454,8 @@ class NonhydrostaticModel:
         if isinstance(closure, AnisotropicMinimumDissipation):
             self.nu_e = FieldView(self, L.F_NU, "nu")
             self.kappa_e = {n: FieldView(self, L.F_KAPPA + i, n) for i, n in enumerate(self.tracer_names)}
+        if smag is not None:
+            self.nu_e, self.kappa_e = FieldView(self, L.F_NU, "nu"), {}   # kappa_e = nu_e / Pr is an operation: no fields
         self.Gn = {n: FieldView(self, L.F_GN + i, n) for i, n in enumerate(names)}
         self.Gm = {n: FieldView(self, L.F_GM + i, n) for i, n in enumerate(names)}
 

@@ -495,6 +495,11 @@ static int update_state(ocn_model* m) {
     for (int t = 0; t < m->nt; ++t) fs[n++] = &m->kappa_e[t];
     if ((rc = fill_fields(m, fs, n))) return rc;
   }
+  if (m->d.closure == OCN_CLOSURE_SMAG) {
+    launch_smag(m);
+    Field* fs[1] = {&m->nu_e};
+    if ((rc = fill_fields(m, fs, 1))) return rc;
+  }
   launch_hydrostatic(m);
   if (m->pHY.present && m->d.buoyancy != OCN_BUOYANCY_NONE) {
     Field* fs[1] = {&m->pHY};
@@ -857,10 +862,8 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-extern "C" {
-
-int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
-  if (!g || !desc || !out) return OCN_EINVAL;
+// ocn_model_create and ocn_model_create_smagorinsky_lilly (smag != null) share this body
+static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
   if (desc->advection < OCN_ADV_NONE || desc->advection > OCN_ADV_U3) return OCN_EINVAL;
@@ -903,6 +906,17 @@ int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   m->ctx = ctx;
   m->d = *desc;
   m->nt = desc->n_tracers;
+  if (smag) {
+    // the molecular part of a (SmagorinskyLilly, ScalarDiffusivity) tuple stays in d.nu / d.kappa; alone: none
+    if (desc->closure == OCN_CLOSURE_NONE) {
+      m->d.nu = 0.0;
+      for (int t = 0; t < OCN_MAX_TRACERS; ++t) m->d.kappa[t] = 0.0;
+    }
+    m->d.closure = OCN_CLOSURE_SMAG;
+    m->smag_C = smag->C;
+    m->smag_Cb = smag->Cb;
+    for (int t = 0; t < m->nt; ++t) m->smag_rPr[t] = 1.0 / smag->Pr[t];
+  }
   m->gd = g->dev;
   m->gd.nb = buffer[desc->advection];
   int rc = 0;
@@ -917,6 +931,8 @@ int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
     rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
     for (int t = 0; t < m->nt; ++t) rc |= field_alloc(m, m->kappa_e[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
   }
+  // DiffusivityFields(grid, tracers, bcs, ::SmagorinskyLilly) (smagorinsky_lilly.jl:209-222): nu_e alone; kappa_e is nu_e / Pr, an operation
+  if (smag) rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
   for (int f = 0; f < 3 + m->nt; ++f) {
     int lx = f == 0, ly = f == 1, lz = f == 2;
     rc |= field_alloc(m, m->Gn[f], lx, ly, lz);
@@ -934,12 +950,13 @@ int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   for (int t = 0; t < m->nt; ++t) default_bcs(m, m->tr[t], false);
   if (m->nu_e.present) {
     default_bcs(m, m->nu_e, true);
-    for (int t = 0; t < m->nt; ++t) default_bcs(m, m->kappa_e[t], true);
+    for (int t = 0; t < m->nt; ++t)
+      if (m->kappa_e[t].present) default_bcs(m, m->kappa_e[t], true);
   }
   // user boundary conditions
   // u, v, w, tracers, then -- AnisotropicMinimumDissipation only -- the diffusivity fields nu_e and kappa_e of every tracer
   // (boundary_conditions = (; kappa_e = (; b = ...)) of the reference: nonhydrostatic_model.jl:150-160, test_boundary_conditions_integration.jl:52-66)
-  const int nbc = 3 + m->nt + (desc->closure == OCN_CLOSURE_AMD ? 1 + m->nt : 0);
+  const int nbc = 3 + m->nt + (smag ? 1 : desc->closure == OCN_CLOSURE_AMD ? 1 + m->nt : 0);
   for (int f = 0; f < nbc; ++f) {
     const int fd = f - (3 + m->nt);   // index among the diffusivity fields
     Field* fld = f == 0 ? &m->u : f == 1 ? &m->v : f == 2 ? &m->w : f < 3 + m->nt ? &m->tr[f - 3] : fd == 0 ? &m->nu_e : &m->kappa_e[fd - 1];
@@ -976,6 +993,13 @@ int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   if (desc->closure == OCN_CLOSURE_AMD && amd_build_table(m) != OCN_OK) {
     ocn_model_destroy(m);
     return OCN_ENOMEM;
+  }
+  if (smag) {
+    const int rs = smag_build_table(m);
+    if (rs != OCN_OK) {
+      ocn_model_destroy(m);
+      return rs;
+    }
   }
   if (hipMalloc((void**)&m->d_red, 64) != hipSuccess) {
     ocn_model_destroy(m);
@@ -1014,6 +1038,50 @@ int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   return OCN_OK;
 }
 
+extern "C" {
+
+int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
+  if (!g || !desc || !out) return OCN_EINVAL;
+  if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
+  return model_create(g, desc, nullptr, out);
+}
+
+int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
+  if (!g || !desc || !smag || !out) return OCN_EINVAL;
+  ocn_ctx* ctx = g->ctx;
+  if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
+  if (desc->closure != OCN_CLOSURE_NONE && desc->closure != OCN_CLOSURE_SCALAR) {
+    ocn_set_error(ctx, "SmagorinskyLilly pairs with nothing or with one ScalarDiffusivity: desc->closure must be OCN_CLOSURE_NONE or OCN_CLOSURE_SCALAR");
+    return OCN_EINVAL;
+  }
+  if (g->topo[0] == OCN_FLAT || g->topo[1] == OCN_FLAT || g->topo[2] == OCN_FLAT) {
+    ocn_set_error(ctx, "SmagorinskyLilly on a grid with a Flat direction is outside the path");
+    return OCN_EUNSUPPORTED;
+  }
+  if (!std::isfinite(smag->C) || !std::isfinite(smag->Cb)) {
+    ocn_set_error(ctx, "SmagorinskyLilly: C and Cb must be finite");
+    return OCN_EINVAL;
+  }
+  for (int t = 0; t < desc->n_tracers; ++t) {
+    if (smag->Pr[t] == 0.0 || !std::isfinite(smag->Pr[t])) {
+      ocn_set_error(ctx, "SmagorinskyLilly: Pr of tracer %d is zero or not finite (kappa_e = nu_e / Pr)", t);
+      return OCN_EINVAL;
+    }
+    for (int s = 0; s < 6; ++s)
+      if (desc->kappa_bcs[t][s].kind != OCN_BC_DEFAULT) {
+        ocn_set_error(ctx, "SmagorinskyLilly has no kappa_e field (kappa_e = nu_e / Pr): boundary conditions for kappa_e cannot apply");
+        return OCN_EINVAL;
+      }
+  }
+  auto ok = [&](int i) { return i >= 0 && i < desc->n_tracers; };
+  if ((desc->buoyancy == OCN_BUOYANCY_TRACER && !ok(desc->b_index)) ||
+      (desc->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(desc->T_index) && ok(desc->S_index)))) {
+    ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
+    return OCN_EINVAL;
+  }
+  return model_create(g, desc, smag, out);
+}
+
 void ocn_model_destroy(ocn_model* m) {
   if (!m) return;
   if (m->ctx->overlap_ready) hipStreamSynchronize(m->ctx->comm_stream);
@@ -1042,6 +1110,7 @@ void ocn_model_destroy(ocn_model* m) {
   hipFree(m->d_red);
   hipFree(m->phi_below);
   hipFree(m->amd_tab);
+  hipFree(m->smag_tab);
   hipFree(m->ypack_s);
   hipFree(m->ypack_r);
   poisson_destroy(m->solver);

@@ -511,11 +511,13 @@ struct RestArgs {
   double *gu, *gv, *gw;
   unsigned org;
   double nu, f;                         // constant viscosity (nue == null), Coriolis parameter
+  double nu0;                           // added to nue: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
   int closure, coriolis, ntiles;
 };
 
-template <int BX, int BY, bool ZB>
+template <int BX, int BY, bool ZB, bool NU0>   // NU0: a.nu0 is added to the eddy viscosity
 __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
+  const double nu0 = NU0 ? a.nu0 : 0.0;
   constexpr int T = BX * BY, NR = BY + 1, SX = BX + 6;      // rows j0-1 .. j0+BY-1; columns -3 .. Nx+2 (the parent row)
   constexpr int WV = BX < OCN_WAVE ? BX : OCN_WAVE, NW = BX / WV, NWV = T / WV;
   constexpr int SLAB = 4 * NR * SX;
@@ -569,7 +571,7 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
     // carried from the level below: own u, v, w, nu and nu of the west / south neighbours; horizontal part + bottom stresses
     const unsigned cb = cxy + (unsigned)k0 * szb - szb;
     double up = ldo(a.u, cb), vp = ldo(a.v, cb), wp = ldo(a.w, cb);
-    double ncp = amd ? ldo(a.nue, cb) : a.nu, nwp = amd ? ldo(a.nue, cb - sxb) : a.nu, nsp = amd ? ldo(a.nue, cb - syb) : a.nu;
+    double ncp = amd ? (NU0 ? ldo(a.nue, cb) + nu0 : ldo(a.nue, cb)) : a.nu, nwp = amd ? (NU0 ? ldo(a.nue, cb - sxb) + nu0 : ldo(a.nue, cb - sxb)) : a.nu, nsp = amd ? (NU0 ? ldo(a.nue, cb - syb) + nu0 : ldo(a.nue, cb - syb)) : a.nu;
     double hu = 0, hv = 0, hw = 0, bu = 0, bv = 0, bw = 0;
     __syncthreads();
     dma(k0, 0);
@@ -602,11 +604,11 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
       }
       const double rzf = ZB ? g_rdzf(g, k) : g.rdz;   // 1 / dz at face k
       const double uc = RS(0, 0, 0), vc = RS(1, 0, 0), wc = RS(2, 0, 0);
-      const double nc = amd ? RS(3, 0, 0) : a.nu, nw = amd ? RS(3, 0, -1) : a.nu, ns = amd ? RS(3, -1, 0) : a.nu;
+      const double nc = amd ? (NU0 ? RS(3, 0, 0) + nu0 : RS(3, 0, 0)) : a.nu, nw = amd ? (NU0 ? RS(3, 0, -1) + nu0 : RS(3, 0, -1)) : a.nu, ns = amd ? (NU0 ? RS(3, -1, 0) + nu0 : RS(3, -1, 0)) : a.nu;
       // stresses nu * S at the west / south / bottom of this cell (level k)
       double t11 = 0, t12 = 0, t13 = 0, t22 = 0, t23 = 0, t33 = 0;
       if (a.closure != OCN_CLOSURE_NONE && do_y) {
-        const double nsw = amd ? RS(3, -1, -1) : a.nu;
+        const double nsw = amd ? (NU0 ? RS(3, -1, -1) + nu0 : RS(3, -1, -1)) : a.nu;
         t12 = 0.25 * ((nsw + ns) + (nw + nc)) * (0.5 * ((uc - RS(0, -1, 0)) * rdy + (vc - RS(1, 0, -1)) * rdx));     // (x-face i, y-face j)
         t22 = ns * ((vc - RS(1, -1, 0)) * rdy);                                                                   // centre j-1
         t23 = 0.25 * ((nsp + ncp) + (ns + nc)) * (0.5 * ((vc - vp) * rzf + (wc - RS(2, -1, 0)) * rdy));             // (y-face j, z-face k)
@@ -810,7 +812,8 @@ struct Tracer3Args {
   const double* kap;                  // KV: the tracer's eddy diffusivity kappa_e (Center field, halos filled)
   double *gn, *cnew;
   unsigned org;
-  double dt, cn, cm, kappa;
+  double dt, cn, cm, kappa;           // KV = 2: kappa is added to the face average of kappa_e (a tuple's ScalarDiffusivity, or 0)
+  double kscale;                      // KV = 2: kappa_e = kscale * kap (SmagorinskyLilly: kap = nu_e, kscale = 1 / Pr)
   int use_m, ntiles, zwrap;
   int rest_shell;   // REST: 1 = only the first and last level of G^n hold anything (boundary fluxes of a Bounded z; no walls in
                     // x / y): the other levels are neither zeroed by the caller nor read here
@@ -819,7 +822,7 @@ struct Tracer3Args {
 // KV: variable diffusivity (AnisotropicMinimumDissipation): -kappa_face dc/dn with kappa_face the two-point average of kappa_e
 // across the face (closure_kernel_operators.jl:43-48, 82-90) rides in the three face fluxes; kappa_e's slab sits in LDS next
 // to the tracer's, its value one level down in a register.
-template <int ADV, int BX, int BY, bool ZB, bool REST, bool IMG, bool KV>
+template <int ADV, int BX, int BY, bool ZB, bool REST, bool IMG, int KV>   // KV 0: constant kappa; 1: kappa_e field; 2: kscale * field + kappa
 __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args a) {
   constexpr int T = BX * BY, NR = BY + 5, SX = BX + 6;
   constexpr int NG = (NR + BY - 1) / BY;
@@ -867,7 +870,7 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
           if (jg > g.Ny + 2) jg = g.Ny + 2;
           const unsigned o = grow + (unsigned)(jg + 3) * syb - 3u * syb + (unsigned)k * szb;
           pf[gq] = ldo(a.c, o);
-          if (KV) pfk[KV ? gq : 0] = ldo(a.kap, o);
+          if (KV) pfk[KV ? gq : 0] = KV == 2 ? a.kscale * ldo(a.kap, o) : ldo(a.kap, o);
         }
       }
     };
@@ -902,7 +905,7 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
     }
     double un = ldo(a.u, cxy + (unsigned)k0 * szb), vn = ldo(a.v, cxy + (unsigned)k0 * szb), wn = ldo(a.w, cxy + (unsigned)k0 * szb);
     double own_h = 0, own_b = 0;
-    double kdn = KV ? ldo(a.kap, cxy + (unsigned)k0 * szb - szb) : 0.0;   // kappa_e one level down
+    double kdn = KV == 2 ? a.kscale * ldo(a.kap, cxy + (unsigned)k0 * szb - szb) : KV ? ldo(a.kap, cxy + (unsigned)k0 * szb - szb) : 0.0;   // kappa_e one level down
     prefetch(k0);
     commit(k0);
     __syncthreads();
@@ -931,7 +934,8 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
       if (!last) {
         if (full) {
           double f = uw * rec(CS(3, 0), CS(3, 1), CS(3, 2), CS(3, 3), CS(3, 4), CS(3, 5), uw);
-          if (KV) f -= 0.5 * (KS(3, 2) + KS(3, 3)) * (CS(3, 3) - CS(3, 2)) * rdx;
+          if (KV == 2) f -= (0.5 * (KS(3, 2) + KS(3, 3)) + a.kappa) * (CS(3, 3) - CS(3, 2)) * rdx;
+          else if (KV) f -= 0.5 * (KS(3, 2) + KS(3, 3)) * (CS(3, 3) - CS(3, 2)) * rdx;
           else if (a.kappa != 0.0) f -= a.kappa * (CS(3, 3) - CS(3, 2)) * rdx;
           fxx[tid] = f;
         }
@@ -940,7 +944,8 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
           if (wy && !in_rec(vs_ > 0.0, j + 1, g.Ny)) r = 0.5 * (CS(2, 3) + CS(3, 3));
           else r = rec(CS(0, 3), CS(1, 3), CS(2, 3), CS(3, 3), CS(4, 3), CS(5, 3), vs_);
           double f = vs_ * r;
-          if (KV) f -= 0.5 * (KS(2, 3) + KS(3, 3)) * (CS(3, 3) - CS(2, 3)) * rdy;
+          if (KV == 2) f -= (0.5 * (KS(2, 3) + KS(3, 3)) + a.kappa) * (CS(3, 3) - CS(2, 3)) * rdy;
+          else if (KV) f -= 0.5 * (KS(2, 3) + KS(3, 3)) * (CS(3, 3) - CS(2, 3)) * rdy;
           else if (a.kappa != 0.0) f -= a.kappa * (CS(3, 3) - CS(2, 3)) * rdy;
           fxy[tid] = f;
         }
@@ -954,7 +959,8 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
         fb = wb * r;
         if (KV) {
           const double kc = KS(3, 3);
-          fb -= 0.5 * (kdn + kc) * (zc[3] - zc[2]) * (ZB ? g_rdzf(g, k) : g.rdz);
+          if (KV == 2) fb -= (0.5 * (kdn + kc) + a.kappa) * (zc[3] - zc[2]) * (ZB ? g_rdzf(g, k) : g.rdz);
+          else fb -= 0.5 * (kdn + kc) * (zc[3] - zc[2]) * (ZB ? g_rdzf(g, k) : g.rdz);
           kdn = kc;
         } else if (a.kappa != 0.0) fb -= a.kappa * (zc[3] - zc[2]) * (ZB ? g_rdzf(g, k) : g.rdz);
       }
@@ -1006,13 +1012,12 @@ bool fused_available(const ocn_model* m) {
   if (!g->z_regular) return false;
   // ScalarDiffusivity (constant nu, kappa) rides in the face fluxes of the fused kernels; other closures, Coriolis and
   // buoyancy take the general path
-  if (m->d.closure == OCN_CLOSURE_AMD || m->d.coriolis_fplane || m->d.buoyancy != OCN_BUOYANCY_NONE) return false;
+  if (m->d.closure == OCN_CLOSURE_AMD || m->d.closure == OCN_CLOSURE_SMAG || m->d.coriolis_fplane || m->d.buoyancy != OCN_BUOYANCY_NONE) return false;
   if (tiled_blocker(m)) return false;
   if (getenv("OCNHIP_NO_FUSED")) return false;   // model creation only
   return true;
 }
 
-bool rest4_ok(const ocn_model* m);
 void fused_describe(const ocn_model* m, char* buf, size_t n) {
   const char* why = tiled_blocker(m);
   if (m->fast_path) {
@@ -1028,9 +1033,13 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
   else if (why) snprintf(buf, n, "general kernels: %s", why);
   else if (m->g->topo[0] == OCN_FLAT || m->g->topo[1] == OCN_FLAT) snprintf(buf, n, "general kernels: Flat x / y slices are outside the tiled kernels");
   else snprintf(buf, n, "general kernels (tiled path disabled or not applicable to this topology / decomposition)");
+  if (m->d.closure == OCN_CLOSURE_SMAG) {
+    const size_t l = strlen(buf);
+    snprintf(buf + l, n - l, "; nu_e: %s", smag_tiled_ok(m) ? "tiled kernel (k_smag_nu)" : "one thread per cell (k_smag_nu_cell)");
+  }
 }
 
-static int fused_cu_count(const ocn_model* m) {
+int fused_cu_count(const ocn_model* m) {
   static int ncu = 0;
   if (!ncu) {
 #ifndef OCN_HOST_EMU
@@ -1060,6 +1069,7 @@ struct FusedShape {
 //   OCNHIP_PRIO=code      wave-priority code (see prio_start; 0 = hardware default)
 //   OCNHIP_NO_GRAPH=1     general path: issue every launch of a step from the host instead of replaying a hipGraph
 //   OCNHIP_LOCALITY=0     k_tend4 with the default cache policy on every stream (tests, same-build A/B; see the kernel's note)
+//   OCNHIP_NO_SMAG_TILED=1  SmagorinskyLilly: the one-thread-per-cell nu_e kernel where k_smag_nu would apply (tests, A/B)
 void fused_read_knobs(ocn_model* m) {
   auto env = [](const char* n, int def) { const char* e = getenv(n); return e ? atoi(e) : def; };
   m->knob_fused_xt = env("OCNHIP_FUSED_XT", 0);
@@ -1073,6 +1083,7 @@ void fused_read_knobs(ocn_model* m) {
   // (256^3: 0.575 ms against 0.590 with the hardware's age order; ten codes tried, all within 0.575 - 0.613)
   { const char* e = getenv("OCNHIP_PRIO"); m->knob_prio = e ? (int)strtol(e, nullptr, 0) : 0x20FF; }
   { const char* e = getenv("OCNHIP_LOCALITY"); m->knob_locality = e ? atoi(e) : 1; }
+  m->knob_no_smag_tiled = env("OCNHIP_NO_SMAG_TILED", 0);
 }
 
 static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
@@ -1246,6 +1257,7 @@ bool launch_rest4(ocn_model* m) {
   a.gu = m->Gn[0].d; a.gv = m->Gn[1].d; a.gw = m->Gn[2].d;
   a.org = (unsigned)((m->u.Hx + m->u.Hy * m->u.sy + m->u.Hz * m->u.sz) * sizeof(double));
   a.nu = m->d.nu;
+  a.nu0 = m->d.closure == OCN_CLOSURE_SMAG ? m->d.nu : 0.0;
   a.f = m->d.f;
   a.closure = m->d.closure;
   a.coriolis = m->d.coriolis_fplane;
@@ -1268,12 +1280,14 @@ bool launch_rest4(ocn_model* m) {
   const dim3 blk(bx, by, 1), grd(nseg, 1, 1);
   hipStream_t s = m->ctx->stream;
   const bool zb = m->g->topo[2] == OCN_BOUNDED;
-#define REST4(BXV, BYV) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false>, grd, blk, s, gd, a); }
+#define REST4N(BXV, BYV, N0) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0>, grd, blk, s, gd, a); }
+#define REST4(BXV, BYV) { if (a.nu0 != 0.0) REST4N(BXV, BYV, true) else REST4N(BXV, BYV, false) }
 #ifdef OCN_HOST_EMU
   if (bx == 16) REST4(16, 4) else
 #endif
   if (bx == 256) REST4(256, 4) else if (bx == 128) REST4(128, 8) else REST4(64, 8)
 #undef REST4
+#undef REST4N
   return true;
 }
 
@@ -1366,13 +1380,16 @@ void launch_tracer3(ocn_model* m, double dt, double cn, double cm, int use_m, bo
     a.gn = m->Gn[3 + t].d;
     a.cnew = m->trs[t].d;
     // the closure's tracer flux rides in the face fluxes: constant kappa (ScalarDiffusivity) or the eddy diffusivity field
-    const bool kv = m->d.closure == OCN_CLOSURE_AMD;
-    a.kappa = m->d.closure == OCN_CLOSURE_SCALAR ? m->d.kappa[t] : 0.0;
-    a.kap = kv ? m->kappa_e[t].d : nullptr;
+    const bool smag = m->d.closure == OCN_CLOSURE_SMAG;   // kappa_e = nu_e / Pr read from nu_e, plus the tuple's constant kappa
+    const int kv = smag ? 2 : m->d.closure == OCN_CLOSURE_AMD ? 1 : 0;   // the kernel's KV
+    a.kappa = (m->d.closure == OCN_CLOSURE_SCALAR || smag) ? m->d.kappa[t] : 0.0;
+    a.kap = smag ? m->nu_e.d : kv ? m->kappa_e[t].d : nullptr;
+    a.kscale = smag ? m->smag_rPr[t] : 1.0;
 #ifdef OCN_HOST_EMU
 #define TR3_EMU16(ADVV, ZBV, RESTV, IMGV) \
-    if (bx == 16) { if (kv) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, true>, grd, blk, s, m->gd, a);  \
-                    else ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, false>, grd, blk, s, m->gd, a); } else
+    if (bx == 16) { if (kv == 2) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 2>, grd, blk, s, m->gd, a);  \
+                    else if (kv) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 1>, grd, blk, s, m->gd, a);   \
+                    else ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 0>, grd, blk, s, m->gd, a); } else
 #else
 #define TR3_EMU16(ADVV, ZBV, RESTV, IMGV)
 #endif
@@ -1382,7 +1399,7 @@ void launch_tracer3(ocn_model* m, double dt, double cn, double cm, int use_m, bo
     else ocn_launch_sync(k_tracer_step3<ADVV, 64, 8, ZBV, RESTV, IMGV, KVV>, grd, blk, s, m->gd, a);
 #define TR3_SHAPES(ADVV, ZBV, RESTV, IMGV)                                                                 \
     TR3_EMU16(ADVV, ZBV, RESTV, IMGV)                                                                      \
-    if (kv) { TR3_BX(ADVV, ZBV, RESTV, IMGV, true) } else { TR3_BX(ADVV, ZBV, RESTV, IMGV, false) }
+    if (kv == 2) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 2) } else if (kv) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 1) } else { TR3_BX(ADVV, ZBV, RESTV, IMGV, 0) }
 #define TR3_MODE(ADVV)                                 \
     if (!rest) { TR3_SHAPES(ADVV, false, false, true) } \
     else if (zb) { TR3_SHAPES(ADVV, true, true, false) } \

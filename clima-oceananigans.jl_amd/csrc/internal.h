@@ -9,6 +9,10 @@
 #include "stencils.h"
 
 #define OCN_NF (3 + OCN_MAX_TRACERS)
+// ocn_model::d.closure of a model made by ocn_model_create_smagorinsky_lilly (never in a caller's ocn_model_desc): the eddy
+// viscosity field nu_e of SmagorinskyLilly; d.nu / d.kappa hold the molecular part of the (SmagorinskyLilly,
+// ScalarDiffusivity) tuple, or zero
+#define OCN_CLOSURE_SMAG 3
 
 struct ProfPhase {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -114,6 +118,10 @@ struct ocn_model {
   int fast_path = 0;        // 1: fused periodic WENO kernels usable
   int bz_fast = 0;          // 1: Bounded z: tiled advection + update kernel on top of the general kernels' other terms
   double* amd_tab = nullptr;     // per-level factors of the AMD predictors (kernels.hip amd_build_table)
+  // SmagorinskyLilly (smagorinsky.hip): C, Cb, 1 / Pr per tracer (kappa_e = nu_e / Pr is never stored) and the per-level table
+  double smag_C = 0, smag_Cb = 0, smag_rPr[OCN_MAX_TRACERS] = {0};
+  double* smag_tab = nullptr;    // [Nz]: (C Delta_f)^2 of interior level k, entry [k] (smag_build_table)
+  int knob_no_smag_tiled = 0;    // OCNHIP_NO_SMAG_TILED=1: the one-thread-per-cell nu_e kernel everywhere (tests, A/B)
   double* phi_below = nullptr;   // (Nx,Ny): top plane of the lower neighbour's pressure (slab runs)
   double *ypack_s = nullptr, *ypack_r = nullptr;   // y-slab halo exchange staging (send / receive)
   size_t ypack_n = 0;
@@ -169,6 +177,11 @@ void launch_maxdiv(ocn_model* m, double* out_dev);
 void launch_amd(ocn_model* m);
 int amd_build_table(ocn_model* m);
 
+// ---- smagorinsky.hip --------------------------------------------------------------------------------
+int smag_build_table(ocn_model* m);
+void launch_smag(ocn_model* m);            // nu_e of SmagorinskyLilly (interior); the caller fills its halos
+bool smag_tiled_ok(const ocn_model* m);    // k_smag_nu applies (else the one-thread-per-cell kernel)
+
 // ---- fused.hip -----------------------------------------------------------------------------------------
 void fused_read_knobs(ocn_model* m);
 void fused_describe(const ocn_model* m, char* buf, size_t n);
@@ -176,6 +189,8 @@ bool fused_available(const ocn_model* m);
 bool fused_bz_available(const ocn_model* m);
 void launch_fused_bz(ocn_model* m, double dt, double cn, double cm, int use_m);
 bool launch_rest4(ocn_model* m);
+bool rest4_ok(const ocn_model* m);         // k_rest4 serves the model's non-advective momentum terms
+int fused_cu_count(const ocn_model* m);    // compute units of the model's device (one workgroup of a marching kernel per CU)
 bool fused_tracer3_ok(const ocn_model* m);
 bool tracer_rest_shell(const ocn_model* m);
 void launch_tracer3(ocn_model* m, double dt, double cn, double cm, int use_m, bool rest);

@@ -20,7 +20,8 @@ struct Phys {
   int coriolis;
   double f;
   const double* pH;     // interior pointer or null
-  const double* nu_e;   // AMD
+  const double* nu_e;   // AMD, SmagorinskyLilly
+  double nu0;           // added to nu_e: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
   int buoyancy, bi, Ti, Si;
   double g, alpha, beta;
 };
@@ -38,15 +39,15 @@ static inline dim3 grid3(const GridDev& g, dim3 b) {   // workgroups are one lev
 }
 
 // viscosity at the four stress locations (closure_kernel_operators.jl:72-90)
-OCN_DEVFN double nu_ccc(const Phys& ph, long p) { return ph.nu_e ? ph.nu_e[p] : ph.nu; }
+OCN_DEVFN double nu_ccc(const Phys& ph, long p) { return ph.nu_e ? ph.nu_e[p] + ph.nu0 : ph.nu; }
 OCN_DEVFN double nu_ffc(const Phys& ph, long p, long sy) {
-  return ph.nu_e ? 0.25 * ((ph.nu_e[p - 1 - sy] + ph.nu_e[p - sy]) + (ph.nu_e[p - 1] + ph.nu_e[p])) : ph.nu;
+  return ph.nu_e ? 0.25 * ((ph.nu_e[p - 1 - sy] + ph.nu_e[p - sy]) + (ph.nu_e[p - 1] + ph.nu_e[p])) + ph.nu0 : ph.nu;
 }
 OCN_DEVFN double nu_fcf(const Phys& ph, long p, long sz) {
-  return ph.nu_e ? 0.25 * ((ph.nu_e[p - 1 - sz] + ph.nu_e[p - sz]) + (ph.nu_e[p - 1] + ph.nu_e[p])) : ph.nu;
+  return ph.nu_e ? 0.25 * ((ph.nu_e[p - 1 - sz] + ph.nu_e[p - sz]) + (ph.nu_e[p - 1] + ph.nu_e[p])) + ph.nu0 : ph.nu;
 }
 OCN_DEVFN double nu_cff(const Phys& ph, long p, long sy, long sz) {
-  return ph.nu_e ? 0.25 * ((ph.nu_e[p - sy - sz] + ph.nu_e[p - sz]) + (ph.nu_e[p - sy] + ph.nu_e[p])) : ph.nu;
+  return ph.nu_e ? 0.25 * ((ph.nu_e[p - sy - sz] + ph.nu_e[p - sz]) + (ph.nu_e[p - sy] + ph.nu_e[p])) + ph.nu0 : ph.nu;
 }
 
 template <int ADV, bool WALLS>
@@ -154,7 +155,7 @@ __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, con
 template <int ADV, bool WALLS>
 __global__ void k_tend_c(GridDev g, const double* __restrict__ u, const double* __restrict__ v,
                          const double* __restrict__ w, const double* __restrict__ q, double kap,
-                         const double* __restrict__ kap_e, int closure, double* __restrict__ Gc) {
+                         const double* __restrict__ kap_e, double ks, int closure, double* __restrict__ Gc) {
   int i, j;
   ocn_cell_ij(i, j);
   const int k = blockIdx.z;   // one level per workgroup: k is wave-uniform, so spacings are scalar loads and 1/dz is computed once per wave
@@ -177,10 +178,11 @@ __global__ void k_tend_c(GridDev g, const double* __restrict__ u, const double* 
     }
   }
   if (closure != OCN_CLOSURE_NONE) {
-    // div q = div(-kappa grad c)  (closure_kernel_operators.jl:43-48)
-    auto kx = [&](long p) { return kap_e ? 0.5 * (kap_e[p - 1] + kap_e[p]) : kap; };
-    auto ky = [&](long p) { return kap_e ? 0.5 * (kap_e[p - sy] + kap_e[p]) : kap; };
-    auto kz = [&](long p) { return kap_e ? 0.5 * (kap_e[p - sz] + kap_e[p]) : kap; };
+    // div q = div(-kappa grad c)  (closure_kernel_operators.jl:43-48).  With a field: kappa_e = ks * kap_e (ks = 1; SmagorinskyLilly:
+    // kap_e is nu_e and ks = 1 / Pr, scaled first, then averaged to the face), plus the constant kap of a tuple's ScalarDiffusivity
+    auto kx = [&](long p) { return kap_e ? 0.5 * (ks * kap_e[p - 1] + ks * kap_e[p]) + kap : kap; };
+    auto ky = [&](long p) { return kap_e ? 0.5 * (ks * kap_e[p - sy] + ks * kap_e[p]) + kap : kap; };
+    auto kz = [&](long p) { return kap_e ? 0.5 * (ks * kap_e[p - sz] + ks * kap_e[p]) + kap : kap; };
     double d = (kx(c + 1) * (q[c + 1] - q[c]) * rdx - kx(c) * (q[c] - q[c - 1]) * rdx) * rdx +
                (ky(c + sy) * (q[c + sy] - q[c]) * rdy - ky(c) * (q[c] - q[c - sy]) * rdy) * rdy;
     if (!zf)
@@ -244,14 +246,17 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
   ph.f = m->d.f;
   ph.pH = m->pHY.present ? m->pHY.interior() : nullptr;
   ph.nu_e = m->nu_e.present ? m->nu_e.interior() : nullptr;
+  const bool smag = m->d.closure == OCN_CLOSURE_SMAG;
+  ph.nu0 = smag ? m->d.nu : 0.0;
   static const dim3 b = tuned_block("OCNHIP_TEND_BLOCK", dim3(64, 4, 1));
   const dim3 gr = grid3(g, b);
   const double *u = m->u.interior(), *v = m->v.interior(), *w = m->w.interior();
   double *Gu = m->Gn[0].interior(), *Gv = m->Gn[1].interior(), *Gw = m->Gn[2].interior();
 #define TEND_TRACER(A, W, t)                                                                               \
-  ocn_launch(k_tend_c<A, W>, gr, b, s, g, u, v, w, (const double*)m->tr[t].interior(), m->d.kappa[t],     \
-             (const double*)(m->kappa_e[t].present ? m->kappa_e[t].interior() : nullptr), m->d.closure, \
-             m->Gn[3 + t].interior());
+  ocn_launch(k_tend_c<A, W>, gr, b, s, g, u, v, w, (const double*)m->tr[t].interior(),                    \
+             (smag || m->d.closure == OCN_CLOSURE_SCALAR) ? m->d.kappa[t] : 0.0,                          \
+             (const double*)(smag ? m->nu_e.interior() : m->kappa_e[t].present ? m->kappa_e[t].interior() : nullptr), \
+             smag ? m->smag_rPr[t] : 1.0, m->d.closure, m->Gn[3 + t].interior());
 #define TEND_LAUNCH(A, W)                                                       \
   if (skip_momentum_advection) { if (!launch_rest4(m)) ocn_launch(k_tend_uvw<ADV_NONE, W>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); }  \
   else ocn_launch(k_tend_uvw<A, W>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw);      \

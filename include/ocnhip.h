@@ -161,6 +161,19 @@ void ocn_grid_destroy(ocn_grid* g);
 
 /* ---- model -------------------------------------------------------------------------------------- */
 int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out);
+/* NonhydrostaticModel(; closure = SmagorinskyLilly(C, Cb, Pr)) -- smagorinsky_lilly.jl:68-69,85-106 -- or the 2-tuple
+ * (SmagorinskyLilly, ScalarDiffusivity) of the reference's ocean-LES regression.  Everything but the closure comes from
+ * `desc`, whose layout is unchanged: desc->closure is OCN_CLOSURE_NONE (SmagorinskyLilly alone) or OCN_CLOSURE_SCALAR
+ * (desc->nu / desc->kappa are the tuple's molecular part; the two flux divergences add).  nu_e is the field OCN_F_NU, filled
+ * with desc->nu_bcs; kappa_e of tracer t is nu_e / Pr[t], an operation on nu_e and not a field, so desc->kappa_bcs must be
+ * all OCN_BC_DEFAULT.  OCN_EUNSUPPORTED: a Flat direction; OCN_EINVAL: any other desc->closure, a Pr that is zero or not
+ * finite, kappa_bcs set. */
+typedef struct ocn_smagorinsky_lilly_desc {
+  double C;                     /* Smagorinsky constant (0.16)                                            */
+  double Cb;                    /* buoyancy multiplier of the stability function (1.0); 0 switches it off */
+  double Pr[OCN_MAX_TRACERS];   /* turbulent Prandtl number per tracer (1.0)                              */
+} ocn_smagorinsky_lilly_desc;
+int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out);
 void ocn_model_destroy(ocn_model* m);
 /* which kernels serve this model, and if not the fastest ones, why (e.g. "general kernels: parent arrays of 2 GiB or
  * more exceed the tiled kernels' 32-bit byte offsets").  Writes at most n bytes incl. the terminating 0. */

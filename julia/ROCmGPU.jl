@@ -227,6 +227,8 @@ kernel_path(model::RM) = (buf = Vector{UInt8}(undef, 256);
 #       bottom, <= 4096 points per direction; settings ignored as the reference ignores them; ocn_ifs_field(ifs, 3:4) are C_NULL: no ∫ᶻA;
 #       ocn_ifs_method(ifs, method, x_path, y_path) tells 0 PCG / 1 FFT and 0 fast / 1 direct transform per direction)
 #   the model handle: ocn_hydro_create_implicit(desc, fs.ifs, h) with desc.free_surface = C_NULL; solver.iteration = ocn_ifs_iterations
+# closure = SmagorinskyLilly(C, Cb, Pr) (or (SmagorinskyLilly, ScalarDiffusivity)) on the NonhydrostaticModel: ocn_model(arch, gridh, m) calls
+#   ocn_model_create_smagorinsky_lilly(gridh, desc, Ref(SmagDesc(C, Cb, Pr...)), h) with desc.closure = NONE (or SCALAR + nu / kappa); model.diffusivity_fields.νₑ wraps OCN_F_NU
 #
 # Launch-bound models (config 1) are replayed from hipGraphs inside ocn_time_step; ocn_model_graph_replays(handle, n, active)
 # reports it.  The library reports OCN_ABI_VERSION through ocn_abi_version(): __init__ compares it with 5.
