@@ -156,6 +156,7 @@ def load():
         "ocn_sefs_substep": (I, [P, D, I]),
         "ocn_sefs_substeps": (I, [P, D, I, I, I]),
         "ocn_sefs_graph_replays": (I, [P, C.POINTER(C.c_int64)]),
+        "ocn_sefs_train_mode": (I, [P, C.POINTER(C.c_int)]),
         "ocn_sefs_barotropic_mode": (I, [P, P, P, I]),
         "ocn_sefs_set_average_to_zero": (I, [P]),
         "ocn_sefs_corrector": (I, [P, P, P]),

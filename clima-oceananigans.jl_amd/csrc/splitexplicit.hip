@@ -108,6 +108,7 @@ struct ocn_sefs {
   struct Train { uint64_t dtau_bits; int first, count, mode; void* exec; };
   std::vector<Train> trains;
   int64_t graph_replays = 0;
+  int last_mode = -1;                                     // form of the last train of substeps (ocn_sefs_train_mode); -1: none yet
 };
 
 static int total_len(int loc, int topo, int N, int H) {
@@ -2317,6 +2318,7 @@ int ocn_sefs_substeps(ocn_sefs* s, double dtau, int first_index, int count, int 
   const bool fuse = fused && sefs_fusable(s);
   const bool one = fuse && fused >= 2;
   const bool multi = one && fused >= 3 && sefs_multi_ok(s) && count >= 2;
+  s->last_mode = multi ? 3 : one ? 2 : fuse ? 1 : 0;
   auto issue = [&]() {
     if (one) {
       // cells neither set ever writes (halo rows behind a wall's first one) must agree between the two sets
@@ -2397,6 +2399,12 @@ int ocn_sefs_substeps(ocn_sefs* s, double dtau, int first_index, int count, int 
 int ocn_sefs_graph_replays(const ocn_sefs* s, int64_t* replays) {
   if (!s || !replays) return OCN_EINVAL;
   *replays = s->graph_replays;
+  return OCN_OK;
+}
+
+int ocn_sefs_train_mode(const ocn_sefs* s, int* mode) {
+  if (!s || !mode) return OCN_EINVAL;
+  *mode = s->last_mode;
   return OCN_OK;
 }
 

@@ -247,6 +247,14 @@ class SplitExplicitFreeSurface:
         check(self.lib.ocn_sefs_graph_replays(self.h, C.byref(n)), self.grid.ctx.h)
         return n.value
 
+    @property
+    def train_mode(self):
+        """the form the last train of substeps took on this grid: 0 the reference's five launches per substep, 1 two launches, 2 one
+        launch, 3 several substeps per launch (k_se_multi); -1 before any train"""
+        m = C.c_int()
+        check(self.lib.ocn_sefs_train_mode(self.h, C.byref(m)), self.grid.ctx.h)
+        return m.value
+
     def barotropic_mode(self, U, V, u, v):
         """barotropic_mode!(U, V, grid, u, v); (U, V) must be this free surface's (state.U, state.V) or (auxiliary.Gᵁ, Gⱽ)"""
         if U is self.U and V is self.V:

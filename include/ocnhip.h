@@ -321,6 +321,10 @@ int ocn_sefs_substep(ocn_sefs* s, double dtau, int substep_index);
  * 0: the reference's five launches. */
 int ocn_sefs_substeps(ocn_sefs* s, double dtau, int first_index, int count, int fused);
 int ocn_sefs_graph_replays(const ocn_sefs* s, int64_t* replays);
+/* the form the last train of substeps (ocn_sefs_substeps, or the sub-cycle of a time step) took on this grid: 0 the reference's five
+ * launches per substep, 1 two launches, 2 one launch, 3 several substeps per launch on tiles with ghost rings; -1 before any train.
+ * Read-only: what was asked for is lowered where the grid does not admit it (Bounded x: 0; fewer than 64 x 16 cells: at most 2). */
+int ocn_sefs_train_mode(const ocn_sefs* s, int* mode);
 /* barotropic_mode!(U, V, grid, u, v) (:76-81): into_forcing == 0 -> state.U, state.V; != 0 -> auxiliary.Gᵁ, Gⱽ */
 int ocn_sefs_barotropic_mode(ocn_sefs* s, const ocn_hfield* u, const ocn_hfield* v, int into_forcing);
 int ocn_sefs_set_average_to_zero(ocn_sefs* s);             /* (:83-87) */
