@@ -807,6 +807,53 @@ struct HyMetric {
   int Nx, Ny, Nz, Hx, Hy, Hz;
 };
 
+// The Coriolis and pressure-gradient terms of G_u and G_v, shared by k_hy_Guv and k_hy_Guv_flux (hymomflux.h).  U(di, dj, dk) and
+// V(di, dj, dk) read u and v around the thread's cell; r is its parent row.  The four metric-weighted interpolations are the ones the
+// vector-invariant advection uses as well.
+template <class FV> OCN_DEVFN double hy_Iy_dxv(const HyMetric& g, int r, const FV& V, int di) {      // I_y^c(dx_q^cfc v) at (i + di, j)
+  OCN_NO_CONTRACT
+  return 0.5 * (g.dxcf[r] * V(di, 0, 0) + g.dxcf[r + 1] * V(di, 1, 0));
+}
+template <class FU> OCN_DEVFN double hy_Ix_dyu(const HyMetric& g, int r, const FU& U, int dj) {      // I_x^c(dy_q^fcc u) at (i, j + dj)
+  OCN_NO_CONTRACT
+  return 0.5 * (g.dyfc[r + dj] * U(0, dj, 0) + g.dyfc[r + dj] * U(1, dj, 0));
+}
+template <class FV> OCN_DEVFN double hy_Ix_dxv(const HyMetric& g, int r, const FV& V, int dj) {      // I_x^f(dx_q^cfc v) at (i, j + dj)
+  OCN_NO_CONTRACT
+  return 0.5 * (g.dxcf[r + dj] * V(-1, dj, 0) + g.dxcf[r + dj] * V(0, dj, 0));
+}
+template <class FU> OCN_DEVFN double hy_Iy_dyu(const HyMetric& g, int r, const FU& U, int di) {      // I_y^f(dy_q^fcc u) at (i + di, j)
+  OCN_NO_CONTRACT
+  return 0.5 * (g.dyfc[r - 1] * U(di, -1, 0) + g.dyfc[r] * U(di, 0, 0));
+}
+struct HyPair { double u, v; };      // the u- and the v-component of a term
+// x_f_cross_U / y_f_cross_U (f_plane.jl:42-43, hydrostatic_spherical_coriolis.jl:29-66)
+// dxfc .. rdycf: the row's spacings and their reciprocals, which the callers hold already
+template <class FU, class FV>
+OCN_DEVFN HyPair hy_coriolis_uv(const HyMetric& g, int cor, double pf0, const double* frow, int r, const FU& U, const FV& V, double dxfc,
+                                double rdxfc, double dycf, double rdycf) {
+  OCN_NO_CONTRACT
+  double Cu = 0.0, Cv = 0.0;
+  if (cor == 3) {
+    Cu = -pf0 * (0.5 * (0.5 * (V(-1, 0, 0) + V(0, 0, 0)) + 0.5 * (V(-1, 1, 0) + V(0, 1, 0))));
+    Cv = pf0 * (0.5 * (0.5 * (U(0, -1, 0) + U(1, -1, 0)) + 0.5 * (U(0, 0, 0) + U(1, 0, 0))));
+  } else if (cor == 1) {
+    const double f0 = frow[r], f1 = frow[r + 1];
+    Cu = hy_div(-(0.5 * (f0 + f1)) * (0.5 * (hy_Iy_dxv(g, r, V, -1) + hy_Iy_dxv(g, r, V, 0))), dxfc, rdxfc);
+    Cv = hy_div(+(0.5 * (f0 + f0)) * (0.5 * (hy_Ix_dyu(g, r, U, -1) + hy_Ix_dyu(g, r, U, 0))), dycf, rdycf);
+  } else if (cor == 2) {
+    const double f0 = frow[r], f1 = frow[r + 1];
+    Cu = hy_div(-(0.5 * (f0 * hy_Ix_dxv(g, r, V, 0) + f1 * hy_Ix_dxv(g, r, V, 1))), dxfc, rdxfc);
+    Cv = hy_div(+(0.5 * (f0 * hy_Iy_dyu(g, r, U, 0) + f0 * hy_Iy_dyu(g, r, U, 1))), dycf, rdycf);
+  }
+  return HyPair{Cu, Cv};
+}
+// d_x pHY' at (Face, Center) and d_y pHY' at (Center, Face); p points at the thread's cell
+OCN_DEVFN HyPair hy_pressure_gradient(const double* p, long syc, double dxfc, double rdxfc, double dycf, double rdycf) {
+  OCN_NO_CONTRACT
+  return HyPair{hy_div(p[0] - p[-1], dxfc, rdxfc), hy_div(p[0] - p[-syc], dycf, rdycf)};
+}
+
 // VS: madv 4 only, WENO5(vector_invariant = VelocityStencil()) -- its own instantiation, so that its wider stencil state does not
 // enter the register allocation of the other flavours (k_hy_Guv<false>: madv 0..3, the same code as without the bound).  Left to
 // itself the compiler gives k_hy_Guv<true> 99 VGPRs (4 waves per SIMD); asked for 5 it fits in 83 without spilling (6: 8 spilled)
@@ -837,10 +884,10 @@ __global__ void __launch_bounds__(256, VS ? 5 : 1) k_hy_Guv(HyMetric g, HyPhys p
   auto Kh = [&](int di, int dj) {
     return (0.5 * (sq(U(di, dj, 0)) + sq(U(di + 1, dj, 0))) + 0.5 * (sq(V(di, dj, 0)) + sq(V(di, dj + 1, 0)))) / 2;
   };
-  auto Iy_dxv = [&](int di) { return 0.5 * (g.dxcf[r] * V(di, 0, 0) + g.dxcf[r + 1] * V(di, 1, 0)); };
-  auto Ix_dyu = [&](int dj) { return 0.5 * (g.dyfc[r + dj] * U(0, dj, 0) + g.dyfc[r + dj] * U(1, dj, 0)); };
-  auto Ix_dxv = [&](int dj) { return 0.5 * (g.dxcf[r + dj] * V(-1, dj, 0) + g.dxcf[r + dj] * V(0, dj, 0)); };
-  auto Iy_dyu = [&](int di) { return 0.5 * (g.dyfc[r - 1] * U(di, -1, 0) + g.dyfc[r] * U(di, 0, 0)); };
+  auto Iy_dxv = [&](int di) { return hy_Iy_dxv(g, r, V, di); };
+  auto Ix_dyu = [&](int dj) { return hy_Ix_dyu(g, r, U, dj); };
+  auto Ix_dxv = [&](int dj) { return hy_Ix_dxv(g, r, V, dj); };
+  auto Iy_dyu = [&](int di) { return hy_Iy_dyu(g, r, U, di); };
   const double dxfc = g.dxfc[r], dycf = g.dycf[r], rdxfc = g.r_dxfc[r], rdycf = g.r_dycf[r];
   auto z2w = [&](int dk) {
     return (0.5 * (g.azcc[r] * W(-1, 0, dk) + g.azcc[r] * W(0, 0, dk))) * hy_div(U(0, 0, dk) - U(0, 0, dk - 1), g.dzf[k + dk], g.r_dzf[k + dk]);
@@ -911,22 +958,10 @@ __global__ void __launch_bounds__(256, VS ? 5 : 1) k_hy_Guv(HyMetric g, HyPhys p
     Au = (vvU + vaU) + bhU;
     Av = (vvV + vaV) + bhV;
   }
-  double Cu = 0.0, Cv = 0.0;
-  if (ph.cor == 3) {
-    Cu = -ph.f0 * (0.5 * (0.5 * (V(-1, 0, 0) + V(0, 0, 0)) + 0.5 * (V(-1, 1, 0) + V(0, 1, 0))));
-    Cv = ph.f0 * (0.5 * (0.5 * (U(0, -1, 0) + U(1, -1, 0)) + 0.5 * (U(0, 0, 0) + U(1, 0, 0))));
-  } else if (ph.cor == 1) {
-    const double f0 = ph.frow[r], f1 = ph.frow[r + 1];
-    Cu = hy_div(-(0.5 * (f0 + f1)) * (0.5 * (Iy_dxv(-1) + Iy_dxv(0))), dxfc, rdxfc);
-    Cv = hy_div(+(0.5 * (f0 + f0)) * (0.5 * (Ix_dyu(-1) + Ix_dyu(0))), dycf, rdycf);
-  } else if (ph.cor == 2) {
-    const double f0 = ph.frow[r], f1 = ph.frow[r + 1];
-    Cu = hy_div(-(0.5 * (f0 * Ix_dxv(0) + f1 * Ix_dxv(1))), dxfc, rdxfc);
-    Cv = hy_div(+(0.5 * (f0 * Iy_dyu(0) + f0 * Iy_dyu(1))), dycf, rdycf);
-  }
-  const double px = hy_div(p[cc] - p[cc - 1], dxfc, rdxfc), py = hy_div(p[cc] - p[cc - syc], dycf, rdycf);
-  Gu[cu] = ((-Au - 0.0) - Cu) - px;
-  Gv[cv] = ((-Av - 0.0) - Cv) - py;
+  const HyPair C = hy_coriolis_uv(g, ph.cor, ph.f0, ph.frow, r, U, V, dxfc, rdxfc, dycf, rdycf);
+  const HyPair gp = hy_pressure_gradient(p + cc, syc, dxfc, rdxfc, dycf, rdycf);
+  Gu[cu] = ((-Au - 0.0) - C.u) - gp.u;
+  Gv[cv] = ((-Av - 0.0) - C.v) - gp.v;
   }
 }
 
@@ -1033,6 +1068,9 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 
 // FluxBoundaryCondition on u, v and the tracers: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
 #include "hyflux.h"
+
+// flux-form momentum advection (Centered, UpwindBiased, WENO5): k_hy_Guv_flux
+#include "hymomflux.h"
 
 // ConvectiveAdjustmentVerticalDiffusivity: k_hy_cv_diff, k_hy_cv_implicit, k_hy_cv_momentum, k_hy_cv_ab2 (its explicit terms: hyclosure.h)
 #include "hyconvect.h"
@@ -1240,6 +1278,7 @@ struct ocn_hydro {
   int bT, bS;                                // indices (into c) of the tracers the buoyancy reads, -1: none
   double *Un = nullptr, *Vn = nullptr;       // barotropic mode of the stepped velocities, kept for the corrector
   HyPhys phys{1, 0, 0, 0, 0, 0, 1, 0.0, nullptr};        // the model's defaults: VectorInvariant(), no Coriolis, CenteredSecondOrder tracers
+  int mflux = 0;                             // flux-form momentum advection instead of phys.madv: 0 off, 1 C2, 2 C4, 3 U1, 4 U3, 5 U5, 6 WENO5
   double* frow = nullptr;
   double chi = 0.1;                          // QuasiAdamsBashforth2TimeStepper's default
   // VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): entry 0 the viscosity, 1 + q the diffusivity of tracer q
@@ -1500,8 +1539,22 @@ static void hydro_tendencies(ocn_hydro* h) {
   ocn_launch(k_hy_Guv<VS>, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d,         \
              (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (long)u->T[0],                     \
              (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1])
-  if (ph.madv == 4) HY_GUV(true);
-  else HY_GUV(false);
+#define HY_GUV_FLUX(ADVV)                                                                                                                  \
+  ocn_launch(k_hy_Guv_flux<ADVV>, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d, \
+             (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (long)u->T[0],                     \
+             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1])
+  switch (h->mflux) {
+    case 1: HY_GUV_FLUX(ADV_C2); break;
+    case 2: HY_GUV_FLUX(ADV_C4); break;
+    case 3: HY_GUV_FLUX(ADV_U1); break;
+    case 4: HY_GUV_FLUX(ADV_U3); break;
+    case 5: HY_GUV_FLUX(ADV_U5); break;
+    case 6: HY_GUV_FLUX(ADV_WENO_Z); break;
+    default:
+      if (ph.madv == 4) HY_GUV(true);
+      else HY_GUV(false);
+  }
+#undef HY_GUV_FLUX
 #undef HY_GUV
   for (size_t q = 0; q < h->c.size(); q += 2) {
     const bool two = q + 1 < h->c.size();
@@ -3034,9 +3087,38 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
     if (int rc = upload(ctx, f, &h->frow)) return rc;
   }
   h->phys.madv = momentum_advection;
+  h->mflux = 0;
   h->phys.cor = coriolis;
   h->phys.tadv = tracer_advection;
   h->phys.f0 = coriolis_parameter;
+  return OCN_OK;
+}
+
+/* flux-form momentum advection (momentum_advection = CenteredSecondOrder() ... WENO5()) in place of the momentum_advection of
+ * ocn_hydro_set_physics, which holds again after scheme 0 or a later ocn_hydro_set_physics */
+int ocn_hydro_set_flux_form_momentum_advection(ocn_hydro* h, int scheme) {
+  if (!h) return OCN_EINVAL;
+  const ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  if (scheme < 0 || scheme > 6) {
+    ocn_set_error(ctx, "ocn_hydro_set_flux_form_momentum_advection: scheme 0..6 (0 off, 1 CenteredSecondOrder, 2 CenteredFourthOrder, "
+                       "3 UpwindBiasedFirstOrder, 4 UpwindBiasedThirdOrder, 5 UpwindBiasedFifthOrder, 6 WENO5)");
+    return OCN_EINVAL;
+  }
+  if (scheme && g->kind == HG_LATLON) {      // hydrostatic_free_surface_model.jl:201-210
+    ocn_set_error(ctx, "ocn_hydro_set_flux_form_momentum_advection: flux-form momentum advection is not allowed on curvilinear grids "
+                       "(a LatitudeLongitudeGrid): use a VectorInvariant scheme");
+    return OCN_EINVAL;
+  }
+  if (scheme) {
+    const int need = (scheme == 1 || scheme == 3) ? 1 : (scheme == 2 || scheme == 4) ? 2 : 3;      // halo the scheme's stencils read
+    if (g->H[0] < need || g->H[1] < need || g->H[2] < need || (g->topo[0] == OCN_PERIODIC && g->N[0] < need)) {
+      ocn_set_error(ctx, "ocn_hydro_set_flux_form_momentum_advection: the stencils of this scheme read %d halo cell(s) in every direction "
+                         "(and as many cells of a Periodic x)", need);
+      return OCN_EINVAL;
+    }
+  }
+  h->mflux = scheme;
   return OCN_OK;
 }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import check
+from ._lib import OcnError, check
 from .api import Bounded, Center, Face, Periodic, default_context
 
 Nothing = "Nothing"
@@ -576,6 +576,17 @@ class LinearDrag:
 
 
 SIDES = ("west", "east", "south", "north", "bottom", "top")     # OCN_WEST .. OCN_TOP
+class SchemeNotAvailable(OcnError, KeyError):
+    """a momentum advection name this state cannot take: the library's refusal (an OcnError with its reason -- the grid is curvilinear,
+    the halo is smaller than the stencils) and, as for any other name set_physics has no entry for, a KeyError"""
+
+    def __str__(self):
+        return str(self.args[0])
+
+
+# momentum_advection names in flux form -> scheme of ocn_hydro_set_flux_form_momentum_advection
+FLUX_FORM_MOMENTUM_ADVECTION = {"CenteredSecondOrder": 1, "CenteredFourthOrder": 2, "UpwindBiasedFirstOrder": 3, "UpwindBiasedThirdOrder": 4,
+                                "UpwindBiasedFifthOrder": 5, "WENO5": 6}
 
 
 class HydrostaticState:
@@ -747,11 +758,16 @@ class HydrostaticState:
         """momentum_advection: None | "VectorInvariantEnstrophyConserving" | "VectorInvariantEnergyConserving" |
         "WENOVectorInvariantVorticityStencil" (WENO5(vector_invariant = VorticityStencil())) |
         "WENOVectorInvariantVelocityStencil" (WENO5(vector_invariant = VelocityStencil()): zeta's WENO5 candidates, weights from the
-        smoothness of the tangential velocities);
+        smoothness of the tangential velocities) | in flux form, on a RectilinearGrid only (the reference's rule), "CenteredSecondOrder"
+        -- the reference model's own default; this class's stays "VectorInvariantEnstrophyConserving" -- | "CenteredFourthOrder" |
+        "UpwindBiasedFirstOrder" | "UpwindBiasedThirdOrder" | "UpwindBiasedFifthOrder" | "WENO5" (Z weights, uniform coefficients);
+        a name the state cannot take raises KeyError: an unknown one, or a flux-form one the library refuses (SchemeNotAvailable, which is
+        an OcnError as well and carries the library's reason);
         coriolis: None | ("HydrostaticSphericalCoriolis", rotation_rate, "EnstrophyConserving" | "EnergyConserving") | ("FPlane", f);
         tracer_advection: None | "CenteredSecondOrder" | "CenteredFourthOrder" | "UpwindBiasedFifthOrder" | "WENO5" """
-        ma = {None: 0, "VectorInvariantEnstrophyConserving": 1, "VectorInvariantEnergyConserving": 2,
-              "WENOVectorInvariantVorticityStencil": 3, "WENOVectorInvariantVelocityStencil": 4}[momentum_advection]
+        flux = FLUX_FORM_MOMENTUM_ADVECTION.get(momentum_advection, 0)
+        ma = 0 if flux else {None: 0, "VectorInvariantEnstrophyConserving": 1, "VectorInvariantEnergyConserving": 2,
+                             "WENOVectorInvariantVorticityStencil": 3, "WENOVectorInvariantVelocityStencil": 4}[momentum_advection]
         ta = {None: 0, "CenteredSecondOrder": 1, "CenteredFourthOrder": 2, "UpwindBiasedFifthOrder": 3, "WENO5": 4}[tracer_advection]
         if coriolis is None:
             ck, cp = 0, 0.0
@@ -761,7 +777,14 @@ class HydrostaticState:
             ck, cp = {"EnstrophyConserving": 1, "EnergyConserving": 2}[coriolis[2]], float(coriolis[1])
         else:
             raise ValueError(f"unsupported coriolis {coriolis!r}")
+        if flux:           # asked first: a refusal leaves the state's physics as they were
+            try:
+                check(self.lib.ocn_hydro_set_flux_form_momentum_advection(self.h, flux), self.grid.ctx.h)
+            except OcnError as e:
+                raise SchemeNotAvailable(f"momentum_advection {momentum_advection!r}: {e}") from None
         check(self.lib.ocn_hydro_set_physics(self.h, ma, ck, cp, ta), self.grid.ctx.h)
+        if flux:           # ocn_hydro_set_physics switched the flux form off
+            check(self.lib.ocn_hydro_set_flux_form_momentum_advection(self.h, flux), self.grid.ctx.h)
         self.momentum_advection, self.coriolis, self.tracer_advection = momentum_advection, coriolis, tracer_advection
 
     def __del__(self):

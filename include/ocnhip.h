@@ -393,6 +393,16 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
  *   Bounded direction (topologically_conditional_interpolation.jl:19-83); halos of 2 / 3 / 3 cells.
  * Defaults of a new handle: 1, 0, 1 -- the reference model's. */
 int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, double coriolis_parameter, int tracer_advection);
+/* momentum_advection = an AbstractAdvectionScheme in flux form: U . grad u = div_Uu, U . grad v = div_Uv
+ * (Advection/vector_invariant_advection.jl:100-101, momentum_advection_operators.jl:52-71) in place of the momentum_advection of
+ * ocn_hydro_set_physics.  scheme: 0 off (that momentum_advection holds again), 1 CenteredSecondOrder() -- the reference model's own
+ * default; bit-exact against the oracle --, 2 CenteredFourthOrder(), 3 UpwindBiasedFirstOrder(), 4 UpwindBiasedThirdOrder(),
+ * 5 UpwindBiasedFifthOrder(), 6 WENO5() (Z weights, uniform coefficients); second order inside the boundary buffer of a Bounded
+ * direction (topologically_conditional_interpolation.jl:19-83).  A later ocn_hydro_set_physics switches it off again.
+ * OCN_EINVAL (text in ocn_last_error) for a scheme outside 0..6, on a LatitudeLongitudeGrid -- flux form is not allowed on curvilinear
+ * grids (hydrostatic_free_surface_model.jl:201-210) -- and for halos smaller than the stencils read: 1 cell for schemes 1 and 3,
+ * 2 for 2 and 4, 3 for 5 and 6 (a Periodic x needs at least as many cells). */
+int ocn_hydro_set_flux_form_momentum_advection(ocn_hydro* h, int scheme);
 /* closure = VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa = (kappa per tracer)) with constant
  * coefficients: implicit_step! of u, v and every tracer inside ab2_step! (hydrostatic_free_surface_ab2_step.jl:72-85,115-128;
  * TurbulenceClosures/vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121); no flux through top
