@@ -172,6 +172,8 @@ def load():
         "ocn_hydro_step_after_tendencies": (I, [P, D, D, I]),
         "ocn_hydro_set_physics": (I, [P, I, I, D, I]),
         "ocn_hydro_set_flux_form_momentum_advection": (I, [P, I]),
+        "ocn_hydro_set_stretched_weno": (I, [P, C.c_int32, C.c_int32]),
+        "ocn_hydro_weno_coefficients": (I, [P, PD, C.c_int64]),
         "ocn_hydro_set_closure": (I, [P, D, I, PD]),
         "ocn_hydro_set_horizontal_closure": (I, [P, D, D, I, PD, PD]),
         "ocn_hydro_set_flux_bc": (I, [P, I, I, I, D, PD, C.c_int64]),

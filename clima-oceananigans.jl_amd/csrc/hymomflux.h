@@ -115,3 +115,62 @@ __global__ void __launch_bounds__(256) k_hy_Guv_flux(HyMetric g, HyPhys ph, cons
     Gv[cv] = ((-Av - 0.0) - C.v) - gp.v;
   }
 }
+
+// Flux-form WENO5(grid = grid) on a stretched z: k_hy_Guv_flux<ADV_WENO_Z> with the candidates of the z reconstructions of Wu and Wv
+// taken from the row of face k of the table tab (hywenoz.h: hy_flux_sz); every other flux, Coriolis and the pressure gradient are the
+// same expressions.  A kernel of its own, so that k_hy_Guv_flux's instantiations keep their code.
+__global__ void __launch_bounds__(256) k_hy_Guv_flux_sz(HyMetric g, HyPhys ph, const double* __restrict__ u, const double* __restrict__ v,
+                                                        const double* __restrict__ w, const double* __restrict__ p, double* __restrict__ Gu,
+                                                        double* __restrict__ Gv, const double* __restrict__ tab, long syu, long szu, long syv,
+                                                        long szv, long syc, long szc) {
+  OCN_NO_CONTRACT
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y;
+  if (i >= g.Nx || j >= g.Ny) return;
+  constexpr int ADV = ADV_WENO_Z, NB = 2;
+  const int r = OCN_UNIFORM(j + g.Hy);       // blockDim.x == 64: one row per wave
+  long cu = (i + g.Hx) + (long)r * syu + (long)g.Hz * szu, cv = (i + g.Hx) + (long)r * syv + (long)g.Hz * szv;
+  long cc = (i + g.Hx) + (long)r * syc + (long)g.Hz * szc;
+  const long szw = szc;
+  auto U = [&](int di, int dj, int dk) { return u[cu + di + dj * syu + dk * szu]; };
+  auto V = [&](int di, int dj, int dk) { return v[cv + di + dj * syv + dk * szv]; };
+  const bool xb = ph.xb != 0, yb = ph.yb != 0;
+  const int ig = i + 1, jg = ph.jrow0 + j + 1;
+  const double dxfc = g.dxfc[r], dycf = g.dycf[r], rdxfc = g.r_dxfc[r], rdycf = g.r_dycf[r];
+  const double dyfc = g.dyfc[r], dxcf = g.dxcf[r], dxcfm = g.dxcf[r - 1], dxcfp = g.dxcf[r + 1], azcc = g.azcc[r];
+  // Wu, Wv through the face below level k + dk; kf: the face's 1-based index, the same in every lane (its table row: scalar loads)
+  auto Wuv = [&](int dk, int kf, double& Wu, double& Wv) {
+    const double* wk = w + cc + dk * szw;
+    const double wx = sym_b<ADV>(wk - 1, 1, xb, ig, g.Nx, NB), wy = sym_b<ADV>(wk - syc, syc, yb, jg, ph.gNy, NB);
+    const double* tk = tab + 12 * OCN_UNIFORM(kf);
+    Wu = azcc * hy_flux_sz(u + cu + dk * szu, szu, wx, kf, g.Nz, tk);
+    Wv = azcc * hy_flux_sz(v + cv + dk * szv, szv, wy, kf, g.Nz, tk);
+  };
+  double Wu_lo, Wv_lo;
+  Wuv(0, 1, Wu_lo, Wv_lo);
+  for (int k = 0; k < g.Nz; ++k, cu += szu, cv += szv, cc += szc) {
+    const double dz = g.dzc[k];
+    double Wu_hi, Wv_hi;
+    Wuv(1, k + 2, Wu_hi, Wv_hi);
+    const double *uc = u + cu, *vc = v + cv;
+    const double ux0 = sym_b<ADV>(uc - 1, 1, xb, ig - 1, g.Nx, NB), ux1 = sym_b<ADV>(uc, 1, xb, ig, g.Nx, NB);
+    const double uFx0 = (dyfc * dz) * hy_flux_b<ADV>(uc, 1, ux0, xb, ig - 1, g.Nx, NB);
+    const double uFx1 = (dyfc * dz) * hy_flux_b<ADV>(uc + 1, 1, ux1, xb, ig, g.Nx, NB);
+    const double vx0 = sym_b<ADV>(vc - 1, 1, xb, ig, g.Nx, NB), vx1 = sym_b<ADV>(vc + syv - 1, 1, xb, ig, g.Nx, NB);
+    const double uFy0 = (dxcf * dz) * hy_flux_b<ADV>(uc, syu, vx0, yb, jg, ph.gNy, NB);
+    const double uFy1 = (dxcfp * dz) * hy_flux_b<ADV>(uc + syu, syu, vx1, yb, jg + 1, ph.gNy, NB);
+    const double Au = 1 / (azcc * dz) * (((uFx1 - uFx0) + (uFy1 - uFy0)) + (Wu_hi - Wu_lo));
+    const double uy0 = sym_b<ADV>(uc - syu, syu, yb, jg, ph.gNy, NB), uy1 = sym_b<ADV>(uc + 1 - syu, syu, yb, jg, ph.gNy, NB);
+    const double vFx0 = (dyfc * dz) * hy_flux_b<ADV>(vc, 1, uy0, xb, ig, g.Nx, NB);
+    const double vFx1 = (dyfc * dz) * hy_flux_b<ADV>(vc + 1, 1, uy1, xb, ig + 1, g.Nx, NB);
+    const double vy0 = sym_b<ADV>(vc - syv, syv, yb, jg - 1, ph.gNy, NB), vy1 = sym_b<ADV>(vc, syv, yb, jg, ph.gNy, NB);
+    const double vFy0 = (dxcfm * dz) * hy_flux_b<ADV>(vc, syv, vy0, yb, jg - 1, ph.gNy, NB);
+    const double vFy1 = (dxcf * dz) * hy_flux_b<ADV>(vc + syv, syv, vy1, yb, jg, ph.gNy, NB);
+    const double Av = 1 / (azcc * dz) * (((vFx1 - vFx0) + (vFy1 - vFy0)) + (Wv_hi - Wv_lo));
+    Wu_lo = Wu_hi;
+    Wv_lo = Wv_hi;
+    const HyPair C = hy_coriolis_uv(g, ph.cor, ph.f0, ph.frow, r, U, V, dxfc, rdxfc, dycf, rdycf);
+    const HyPair gp = hy_pressure_gradient(p + cc, syc, dxfc, rdxfc, dycf, rdycf);
+    Gu[cu] = ((-Au - 0.0) - C.u) - gp.u;
+    Gv[cv] = ((-Av - 0.0) - C.v) - gp.v;
+  }
+}

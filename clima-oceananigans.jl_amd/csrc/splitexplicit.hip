@@ -1069,7 +1069,10 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 // FluxBoundaryCondition on u, v and the tracers: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
 #include "hyflux.h"
 
-// flux-form momentum advection (Centered, UpwindBiased, WENO5): k_hy_Guv_flux
+// WENO5(grid = grid) on a stretched z: the coefficient table, recon5_sz, k_hy_Gc_sz
+#include "hywenoz.h"
+
+// flux-form momentum advection (Centered, UpwindBiased, WENO5): k_hy_Guv_flux, k_hy_Guv_flux_sz
 #include "hymomflux.h"
 
 // ConvectiveAdjustmentVerticalDiffusivity: k_hy_cv_diff, k_hy_cv_implicit, k_hy_cv_momentum, k_hy_cv_ab2 (its explicit terms: hyclosure.h)
@@ -1279,6 +1282,11 @@ struct ocn_hydro {
   double *Un = nullptr, *Vn = nullptr;       // barotropic mode of the stepped velocities, kept for the corrector
   HyPhys phys{1, 0, 0, 0, 0, 0, 1, 0.0, nullptr};        // the model's defaults: VectorInvariant(), no Coriolis, CenteredSecondOrder tracers
   int mflux = 0;                             // flux-form momentum advection instead of phys.madv: 0 off, 1 C2, 2 C4, 3 U1, 4 U3, 5 U5, 6 WENO5
+  // WENO5(grid = grid): the stretched-z candidates for the WENO5 tracer scheme / the flux-form WENO5 momentum scheme; the table
+  // ((Nz + 2) x 4 x 3, hywenoz.h) exists while either is on and z is stretched -- a regular z keeps the uniform kernels
+  bool sz_tracers = false, sz_momentum = false;
+  std::vector<double> sz_host;
+  double* sz_tab = nullptr;
   double* frow = nullptr;
   double chi = 0.1;                          // QuasiAdamsBashforth2TimeStepper's default
   // VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): entry 0 the viscosity, 1 + q the diffusivity of tracer q
@@ -1549,7 +1557,13 @@ static void hydro_tendencies(ocn_hydro* h) {
     case 3: HY_GUV_FLUX(ADV_U1); break;
     case 4: HY_GUV_FLUX(ADV_U3); break;
     case 5: HY_GUV_FLUX(ADV_U5); break;
-    case 6: HY_GUV_FLUX(ADV_WENO_Z); break;
+    case 6:
+      if (h->sz_momentum && h->sz_tab && g->N[2] > 3)      // up to three levels every z face lies inside the boundary buffer: nothing reads the table
+        ocn_launch(k_hy_Guv_flux_sz, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d,
+                   (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (const double*)h->sz_tab,
+                   (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
+      else HY_GUV_FLUX(ADV_WENO_Z);
+      break;
     default:
       if (ph.madv == 4) HY_GUV(true);
       else HY_GUV(false);
@@ -1565,6 +1579,17 @@ static void hydro_tendencies(ocn_hydro* h) {
       // CenteredFourthOrder / UpwindBiasedFifthOrder / WENO5
       const int xb = g->topo[0] != OCN_PERIODIC, yb = g->topo[1] != OCN_PERIODIC;
       const dim3 grh((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);          // one thread per column
+      if (tadv == 4 && h->sz_tracers && h->sz_tab && g->N[2] > 3) {      // Nz <= 3: no z face outside the buffer, the uniform kernel is the scheme
+        if (two)
+          ocn_launch(k_hy_Gc_sz<2>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1,
+                     G0, G1, (const double*)h->sz_tab, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
+                     (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
+        else
+          ocn_launch(k_hy_Gc_sz<1>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1,
+                     G0, G1, (const double*)h->sz_tab, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
+                     (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
+        continue;
+      }
 #define HY_GC_HI(ADVV)                                                                                                                     \
   if (two)                                                                                                                                 \
     ocn_launch(k_hy_Gc_hi<ADVV, 2>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d,  \
@@ -2655,6 +2680,7 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   hipFree(h->Un);
   hipFree(h->Vn);
   hipFree(h->frow);
+  hipFree(h->sz_tab);
   for (auto& e : h->imptab) hipFree(e.d);
   for (auto& f : h->fbc)
     for (auto& b : f) hipFree(b.d);
@@ -3088,6 +3114,7 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
   }
   h->phys.madv = momentum_advection;
   h->mflux = 0;
+  h->sz_tracers = h->sz_momentum = false;      // WENO5(grid = grid) is asked for again after the schemes are set
   h->phys.cor = coriolis;
   h->phys.tadv = tracer_advection;
   h->phys.f0 = coriolis_parameter;
@@ -3119,7 +3146,49 @@ int ocn_hydro_set_flux_form_momentum_advection(ocn_hydro* h, int scheme) {
     }
   }
   h->mflux = scheme;
+  h->sz_momentum = false;      // WENO5(grid = grid) is asked for after the scheme (ocn_hydro_set_stretched_weno)
   return OCN_OK;
+}
+
+/* WENO5(grid = grid) (ocnhip.h) */
+int ocn_hydro_set_stretched_weno(ocn_hydro* h, int32_t tracers, int32_t momentum) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  if (tracers && h->phys.tadv != 4) {
+    ocn_set_error(ctx, "ocn_hydro_set_stretched_weno: the tracer advection scheme is not WENO5 (tracer_advection %d)", h->phys.tadv);
+    return OCN_EINVAL;
+  }
+  if (momentum && h->mflux != 6) {
+    ocn_set_error(ctx, "ocn_hydro_set_stretched_weno: the momentum advection scheme is not the flux-form WENO5 (scheme 6 of "
+                       "ocn_hydro_set_flux_form_momentum_advection)");
+    return OCN_EINVAL;
+  }
+  if ((tracers || momentum) && (g->H[0] < 3 || g->H[1] < 3 || g->H[2] < 3)) {
+    ocn_set_error(ctx, "ocn_hydro_set_stretched_weno: the WENO5 stencils read 3 halo cells in every direction");
+    return OCN_EINVAL;
+  }
+  const bool want = (tracers || momentum) && !g->z_regular;       // a regular z has no table (weno_fifth_order.jl:555-556)
+  if (want && !h->sz_tab) {
+    h->sz_host = hy_weno_table(g->nodeF[2]);
+    if (int rc = upload(ctx, h->sz_host, &h->sz_tab)) return rc;
+  }
+  if (!want && h->sz_tab) {
+    OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    hipFree(h->sz_tab);
+    h->sz_tab = nullptr;
+    h->sz_host.clear();
+  }
+  h->sz_tracers = tracers != 0;
+  h->sz_momentum = momentum != 0;
+  return OCN_OK;
+}
+
+int ocn_hydro_weno_coefficients(ocn_hydro* h, double* out, int64_t n) {
+  if (!h || n < 0 || (n > 0 && !out)) return OCN_EINVAL;
+  const int64_t have = (h->sz_tracers || h->sz_momentum) ? (int64_t)h->sz_host.size() : 0;      // kept for reuse while switched off
+  for (int64_t q = 0; q < n && q < have; ++q) out[q] = h->sz_host[q];
+  return (int)have;
 }
 
 int ocn_hydro_calculate_tendencies(ocn_hydro* h) {

@@ -576,6 +576,13 @@ class LinearDrag:
 
 
 SIDES = ("west", "east", "south", "north", "bottom", "top")     # OCN_WEST .. OCN_TOP
+def check_count(rc, ctx):
+    """a call that returns a count (>= 0) or an error code (< 0)"""
+    if rc < 0:
+        check(rc, ctx)
+    return rc
+
+
 class SchemeNotAvailable(OcnError, KeyError):
     """a momentum advection name this state cannot take: the library's refusal (an OcnError with its reason -- the grid is curvilinear,
     the halo is smaller than the stencils) and, as for any other name set_physics has no entry for, a KeyError"""
@@ -587,6 +594,45 @@ class SchemeNotAvailable(OcnError, KeyError):
 # momentum_advection names in flux form -> scheme of ocn_hydro_set_flux_form_momentum_advection
 FLUX_FORM_MOMENTUM_ADVECTION = {"CenteredSecondOrder": 1, "CenteredFourthOrder": 2, "UpwindBiasedFirstOrder": 3, "UpwindBiasedThirdOrder": 4,
                                 "UpwindBiasedFifthOrder": 5, "WENO5": 6}
+
+
+class WENO5:
+    """WENO5(grid = nothing, stretched_smoothness = false, zweno = true) (Advection/weno_fifth_order.jl:164-180) as tracer_advection or,
+    in flux form, momentum_advection of a HydrostaticState.  WENO5() is the string "WENO5": uniform coefficients.  WENO5(grid=g) takes
+    the candidates of the z reconstructions from the table of g's stretched z faces (ocn_hydro_set_stretched_weno); g is the state's
+    grid or, for a latitude band, its whole grid.  A grid whose z was given as an extent is regular and has no table, as in the
+    reference: the scheme is then the uniform one.  The library carries the default smoothness indicators and the Z weights only:
+    stretched_smoothness=True and zweno=False raise ValueError."""
+
+    def __init__(self, grid=None, stretched_smoothness=False, zweno=True):
+        if stretched_smoothness:
+            raise ValueError("WENO5(stretched_smoothness=True) is not available: the library carries the Jiang-Shu smoothness indicators "
+                             "(the reference's default) only; see DESIGN.md")
+        if not zweno:
+            raise ValueError("WENO5(zweno=False) is not available: the hydrostatic kernels carry the Z weights only")
+        if grid is not None and not isinstance(grid, _HGrid):
+            raise ValueError("WENO5(grid=...): an HRectilinearGrid or a LatitudeLongitudeGrid of this module")
+        self.grid = grid
+
+    def __repr__(self):
+        return "WENO5()" if self.grid is None else "WENO5(grid=grid)"
+
+
+def _same_domain(a, b):
+    """whether two grid objects describe the same whole grid (a band's constructor arguments are its whole grid's)"""
+    (ca, ka), (cb, kb) = a._ctor, b._ctor
+    if ca is not cb:
+        return False
+    for key, va in ka.items():
+        if key == "arch":
+            continue
+        vb = kb[key]
+        if key == "topology":
+            if tuple(va) != tuple(vb):
+                return False
+        elif not np.array_equal(np.asarray(va, dtype=np.float64), np.asarray(vb, dtype=np.float64)):
+            return False
+    return True
 
 
 class HydrostaticState:
@@ -764,7 +810,12 @@ class HydrostaticState:
         a name the state cannot take raises KeyError: an unknown one, or a flux-form one the library refuses (SchemeNotAvailable, which is
         an OcnError as well and carries the library's reason);
         coriolis: None | ("HydrostaticSphericalCoriolis", rotation_rate, "EnstrophyConserving" | "EnergyConserving") | ("FPlane", f);
-        tracer_advection: None | "CenteredSecondOrder" | "CenteredFourthOrder" | "UpwindBiasedFifthOrder" | "WENO5" """
+        tracer_advection: None | "CenteredSecondOrder" | "CenteredFourthOrder" | "UpwindBiasedFifthOrder" | "WENO5";
+        momentum_advection and tracer_advection also take a WENO5 object: WENO5() is "WENO5", WENO5(grid=grid) the same scheme with the
+        stretched-z coefficients of the state's grid (ValueError for any other grid)"""
+        given = (momentum_advection, tracer_advection)
+        momentum_advection, stretched_m = self._weno_scheme(momentum_advection, "momentum_advection")
+        tracer_advection, stretched_t = self._weno_scheme(tracer_advection, "tracer_advection")
         flux = FLUX_FORM_MOMENTUM_ADVECTION.get(momentum_advection, 0)
         ma = 0 if flux else {None: 0, "VectorInvariantEnstrophyConserving": 1, "VectorInvariantEnergyConserving": 2,
                              "WENOVectorInvariantVorticityStencil": 3, "WENOVectorInvariantVelocityStencil": 4}[momentum_advection]
@@ -785,7 +836,28 @@ class HydrostaticState:
         check(self.lib.ocn_hydro_set_physics(self.h, ma, ck, cp, ta), self.grid.ctx.h)
         if flux:           # ocn_hydro_set_physics switched the flux form off
             check(self.lib.ocn_hydro_set_flux_form_momentum_advection(self.h, flux), self.grid.ctx.h)
-        self.momentum_advection, self.coriolis, self.tracer_advection = momentum_advection, coriolis, tracer_advection
+        if stretched_m or stretched_t:      # ocn_hydro_set_physics switched the stretched coefficients off
+            check(self.lib.ocn_hydro_set_stretched_weno(self.h, int(stretched_t), int(stretched_m)), self.grid.ctx.h)
+        self.momentum_advection, self.coriolis, self.tracer_advection = given[0], coriolis, given[1]
+
+    def _weno_scheme(self, scheme, what):
+        """(name, stretched) of a scheme given as a name or as a WENO5 object"""
+        if not isinstance(scheme, WENO5):
+            return scheme, False
+        if scheme.grid is None:
+            return "WENO5", False
+        if not _same_domain(scheme.grid, self.grid):
+            raise ValueError(f"{what} = WENO5(grid=grid): the scheme was built for another grid than the state's")
+        return "WENO5", True
+
+    def weno_coefficients(self):
+        """the (Nz + 2, 4, 3) table of WENO5(grid=grid) -- faces 0 .. Nz + 1, stencils r = -1, 0, 1, 2 -- or None while there is none"""
+        n = check_count(self.lib.ocn_hydro_weno_coefficients(self.h, None, 0), self.grid.ctx.h)
+        if n == 0:
+            return None
+        out = np.zeros(n)
+        check_count(self.lib.ocn_hydro_weno_coefficients(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), n), self.grid.ctx.h)
+        return out.reshape(-1, 4, 3)
 
     def __del__(self):
         try:

@@ -403,6 +403,20 @@ int ocn_hydro_set_physics(ocn_hydro* h, int momentum_advection, int coriolis, do
  * grids (hydrostatic_free_surface_model.jl:201-210) -- and for halos smaller than the stencils read: 1 cell for schemes 1 and 3,
  * 2 for 2 and 4, 3 for 5 and 6 (a Periodic x needs at least as many cells). */
 int ocn_hydro_set_flux_form_momentum_advection(ocn_hydro* h, int scheme);
+/* WENO5(grid = grid) on a vertically stretched grid (Advection/weno_fifth_order.jl:182-209,526-539,562-584,740-772): the candidate
+ * polynomials of the z reconstructions take their coefficients from coeff_z^aaf -- interp_weights over the faces of
+ * with_halo((4, 4, 4), grid), stencils r = -1, 0, 1, 2 at the faces 0 .. Nz + 1, read at the face's own index -- in place of 1/3, 5/6,
+ * -1/6, ...; x, y, longitude and latitude are regular on these grids and keep the uniform constants, as do the smoothness indicators
+ * (stretched_smoothness = false) and the Z weights.  tracers != 0: for the WENO5 tracer scheme (tracer_advection 4 of
+ * ocn_hydro_set_physics), on either grid; momentum != 0: for the flux-form WENO5 momentum scheme (scheme 6 of
+ * ocn_hydro_set_flux_form_momentum_advection).  The table is computed on the host by this call.  On a grid whose z is regular (given
+ * as an extent) there is no table, as in the reference, and the uniform kernels keep running.  ocn_hydro_set_physics switches both
+ * off, ocn_hydro_set_flux_form_momentum_advection the momentum one: ask again after the schemes are set.
+ * OCN_EINVAL (text in ocn_last_error) when the corresponding scheme is not WENO5, or with fewer than 3 halo cells. */
+int ocn_hydro_set_stretched_weno(ocn_hydro* h, int32_t tracers, int32_t momentum);
+/* the table of ocn_hydro_set_stretched_weno, for tests: (Nz + 2) x 4 x 3 doubles, [face 0 .. Nz + 1][r = -1, 0, 1, 2][cell of the
+ * stencil], last index fastest.  Copies min(n, entries) doubles and returns the number of entries: 0 while there is no table. */
+int ocn_hydro_weno_coefficients(ocn_hydro* h, double* out, int64_t n);
 /* closure = VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa = (kappa per tracer)) with constant
  * coefficients: implicit_step! of u, v and every tracer inside ab2_step! (hydrostatic_free_surface_ab2_step.jl:72-85,115-128;
  * TurbulenceClosures/vertically_implicit_diffusion_solver.jl:46-100, Solvers/batched_tridiagonal_solver.jl:89-121); no flux through top
