@@ -176,6 +176,8 @@ def load():
         "ocn_hydro_weno_coefficients": (I, [P, PD, C.c_int64]),
         "ocn_hydro_set_closure": (I, [P, D, I, PD]),
         "ocn_hydro_set_horizontal_closure": (I, [P, D, D, I, PD, PD]),
+        "ocn_hydro_set_horizontal_formulation": (I, [P, I, I]),
+        "ocn_hydro_set_horizontal_coefficient_table": (I, [P, I, I, PD, PD, I, I]),
         "ocn_hydro_set_flux_bc": (I, [P, I, I, I, D, PD, C.c_int64]),
         "ocn_hydro_set_convective_adjustment": (I, [P, I, D, D, D, D, I, C.POINTER(C.c_int32)]),
         "ocn_hydro_set_ri_based_diffusivity": (I, [P, I, I, I, D, D, D, D, D, D, I, C.POINTER(C.c_int32)]),

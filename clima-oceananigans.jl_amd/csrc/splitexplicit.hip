@@ -1065,6 +1065,8 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 
 // HorizontalScalarDiffusivity and HorizontalScalarBiharmonicDiffusivity: k_hy_clo_uv, k_hy_clo_c
 #include "hyclosure.h"
+// the same closures with (row, level) coefficient tables and the HorizontalDivergence formulations: k_hy_clo_uv_var, k_hy_clo_c_var
+#include "hyclosure_var.h"
 
 // FluxBoundaryCondition on u, v and the tracers: k_hy_flux_x, k_hy_flux_y, k_hy_flux_z
 #include "hyflux.h"
@@ -1296,6 +1298,15 @@ struct ocn_hydro {
   // HorizontalScalarDiffusivity(nu2, kappa2) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4), explicit: entry 0 of kap2 / kap4 the
   // viscosity, 1 + q the diffusivity of tracer q; empty or all zeros: off
   std::vector<double> kap2, kap4;
+  // coefficients that follow the grid (hyclosure_var.h): per closure order (0 Laplacian, 1 biharmonic) and entry of kap2 / kap4, the two
+  // location tables on the device (rows x Nz each, rows = Ny + 2 Hy + 1), null where the coefficient is the number; hform the
+  // formulation of each order (0 Horizontal, 1 HorizontalDivergence)
+  struct CoefTab { double *a = nullptr, *b = nullptr; };
+  std::vector<CoefTab> ctab[2];
+  int hform[2] = {0, 0};
+  // a number that shares one of those launches with a table or a divergence formulation: one constant table per value, kept by the
+  // setters for every number of kap2 / kap4 while any table or formulation is set
+  std::vector<std::pair<double, double*>> cconst;
   // FluxBoundaryCondition per field (0 u, 1 v, 2 + q tracer q) and side (OCN_WEST .. OCN_TOP); empty: none anywhere.  An array (kind 2)
   // lives on the device and is kept for reuse when the condition is replaced
   struct FluxBC { int kind = 0; double value = 0.0; double* d = nullptr; };
@@ -1309,6 +1320,9 @@ struct ocn_hydro {
     int disc = 0;
     double kc = 0.0, nuc = 0.0, kb = 0.0, nub = 0.0;
     int order[3] = {0, 1, 2};
+    // the same for the tracers: a tuple may hold a Horizontal and a HorizontalDivergence closure of one order, the first with the
+    // tracers' kappa and the second with the momentum's nu, at different positions
+    int order_c[3] = {0, 1, 2};
     ocn_hfield *kap = nullptr, *nu = nullptr;
     double* t = nullptr;
     int loc = 0, taper = 0;
@@ -1618,6 +1632,22 @@ static void hydro_tendencies(ocn_hydro* h) {
 // the explicit terms of a ConvectiveAdjustmentVerticalDiffusivity ride in the same pass as new instances (VZ = 1 explicit, 2 the
 // implicit form's w-shear of u and v), summed with the others in tuple order; nothing new is launched without them
 // (VZ 3 / 4 for the Center-location coefficients of a RiBasedVerticalDiffusivity)
+// a coefficient of closure order o (0 Laplacian, 1 biharmonic), entry q of kap2 / kap4: whether it has tables, whether it is on, and
+// what the kernels of hyclosure_var.h read: its tables, or the constant table of its number
+static bool hydro_coef_table(const ocn_hydro* h, int o, size_t q) { return q < h->ctab[o].size() && h->ctab[o][q].a; }
+static double hydro_coef_number(const ocn_hydro* h, int o, size_t q) {
+  const std::vector<double>& v = o ? h->kap4 : h->kap2;
+  return q < v.size() ? v[q] : 0.0;
+}
+static bool hydro_coef_on(const ocn_hydro* h, int o, size_t q) { return hydro_coef_table(h, o, q) || hydro_coef_number(h, o, q) != 0.0; }
+static HyCoef hydro_coef(const ocn_hydro* h, int o, size_t q) {
+  if (hydro_coef_table(h, o, q)) return HyCoef{h->ctab[o][q].a, h->ctab[o][q].b};
+  const double x = hydro_coef_number(h, o, q);
+  for (const auto& e : h->cconst)
+    if (e.first == x) return HyCoef{e.second, e.second};
+  return HyCoef{nullptr, nullptr};       // not reached: hydro_constant_tables ran when the launch became one of hyclosure_var.h's
+}
+
 static void hydro_horizontal_closures(ocn_hydro* h) {
   static const ocn_hydro::Cavd off{};
   const ocn_hydro::Cavd& cv = hydro_vk(h) ? *hydro_vk(h) : off;
@@ -1636,7 +1666,11 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
                   cv.order[0], cv.order[1], cv.order[2]};
     zc = zu;
     zc.K = cv.kap->d;
+    zc.o0 = cv.order_c[0]; zc.o1 = cv.order_c[1]; zc.o2 = cv.order_c[2];
   }
+  // a viscosity table or a divergence formulation: the instances of hyclosure_var.h; every other launch below is as it was
+  const bool uvar = hydro_coef_table(h, 0, 0) || hydro_coef_table(h, 1, 0) || (h->hform[0] && hydro_coef_on(h, 0, 0)) ||
+                    (h->hform[1] && hydro_coef_on(h, 1, 0));
 #define HY_CLO_UV(LAP, BIH)                                                                                                                \
   ocn_launch(k_hy_clo_uv<LAP, BIH>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d, h->gn[0]->d, \
              h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], HyCvTerm{})
@@ -1648,7 +1682,12 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
   else if (nu != 0.0) HY_CLO_UVZ(true, false, VZ);                                                                                         \
   else if (nu4 != 0.0) HY_CLO_UVZ(false, true, VZ);                                                                                        \
   else HY_CLO_UVZ(false, false, VZ);
-  if (vzu == 1) { HY_CLO_UV3(1) }
+  if (uvar) {
+    const HyCloUVArgs a{hy_metric(g), m, hydro_coef(h, 0, 0), hydro_coef(h, 1, 0), g->N[1] + 2 * g->H[1] + 1, u->d, v->d, h->gn[0]->d, h->gn[1]->d,
+                        (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], zu};
+    hy_clo_uv_var(vzu, hydro_coef_on(h, 0, 0), hydro_coef_on(h, 1, 0), h->hform[0] != 0, h->hform[1] != 0, gr, b, g->ctx->stream, a);
+  }
+  else if (vzu == 1) { HY_CLO_UV3(1) }
   else if (vzu == 2) { HY_CLO_UV3(2) }
   else if (vzu == 3) { HY_CLO_UV3(3) }
   else if (vzu == 4) { HY_CLO_UV3(4) }
@@ -1664,6 +1703,15 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
     const double k0 = hz ? h->kap2[1 + q] : 0.0, k1 = hz && two ? h->kap2[2 + q] : 0.0, k40 = hz ? h->kap4[1 + q] : 0.0,
                  k41 = hz && two ? h->kap4[2 + q] : 0.0;
     const bool lap = k0 != 0.0 || k1 != 0.0, bih = k40 != 0.0 || k41 != 0.0;
+    if (hydro_coef_table(h, 0, 1 + q) || hydro_coef_table(h, 1, 1 + q) || (two && (hydro_coef_table(h, 0, 2 + q) || hydro_coef_table(h, 1, 2 + q)))) {
+      const ocn_hfield* c = h->c[q];
+      const HyCloCArgs a{hy_metric(g), m, HyCoef2{{hydro_coef(h, 0, 1 + q), two ? hydro_coef(h, 0, 2 + q) : HyCoef{}}},
+                         HyCoef2{{hydro_coef(h, 1, 1 + q), two ? hydro_coef(h, 1, 2 + q) : HyCoef{}}}, g->N[1] + 2 * g->H[1] + 1, c->d, two ? h->c[q + 1]->d : nullptr,
+                         h->gn[2 + q]->d, two ? h->gn[3 + q]->d : nullptr, (long)c->T[0], (long)c->T[0] * c->T[1], zc};
+      hy_clo_c_var(vzc, two, hydro_coef_on(h, 0, 1 + q) || (two && hydro_coef_on(h, 0, 2 + q)),
+                   hydro_coef_on(h, 1, 1 + q) || (two && hydro_coef_on(h, 1, 2 + q)), gr, b, g->ctx->stream, a);
+      continue;
+    }
     if (vzc) {
       const ocn_hfield* c = h->c[q];
       const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
@@ -2682,6 +2730,9 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   hipFree(h->frow);
   hipFree(h->sz_tab);
   for (auto& e : h->imptab) hipFree(e.d);
+  for (auto& t : h->ctab)
+    for (auto& e : t) { hipFree(e.a); hipFree(e.b); }
+  for (auto& e : h->cconst) hipFree(e.second);
   for (auto& f : h->fbc)
     for (auto& b : f) hipFree(b.d);
   for (ocn_hydro::Cavd* v : {&h->cv, &h->rb}) {
@@ -2805,6 +2856,44 @@ int ocn_hydro_set_closure(ocn_hydro* h, double nu, int ntracers, const double* k
   return OCN_OK;
 }
 
+static void hydro_clear_coefficient_tables(ocn_hydro* h) {
+  bool any = false;
+  for (auto& t : h->ctab)
+    for (auto& e : t) any = any || e.a;
+  if (any || !h->cconst.empty()) hipStreamSynchronize(h->lg->ctx->stream);        // a step already queued may still read them
+  for (auto& t : h->ctab) {
+    for (auto& e : t) { hipFree(e.a); hipFree(e.b); }
+    t.clear();
+  }
+  for (auto& e : h->cconst) hipFree(e.second);
+  h->cconst.clear();
+  h->hform[0] = h->hform[1] = 0;
+}
+// a constant table for every number of kap2 / kap4 (the zeros of fields that are off included: a pair of tracers shares a launch)
+static int hydro_constant_tables(ocn_hydro* h) {
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const size_t n = (size_t)(g->N[1] + 2 * g->H[1] + 1) * g->N[2];
+  const size_t nf = 1 + h->c.size();
+  for (int o = 0; o < 2; ++o) {
+    for (size_t q = 0; q < nf; ++q) {
+      const double x = hydro_coef_number(h, o, q);
+      bool have = false;
+      for (const auto& e : h->cconst) have = have || e.first == x;
+      if (have) continue;
+      double* d = nullptr;
+      if (hipMalloc((void**)&d, n * sizeof(double)) != hipSuccess) {
+        ocn_set_error(ctx, "allocation of %zu bytes failed", n * sizeof(double));
+        return OCN_ENOMEM;
+      }
+      h->cconst.emplace_back(x, d);
+      const std::vector<double> host(n, x);
+      OCN_HIP_CHECK(ctx, hipMemcpy(d, host.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  return OCN_OK;
+}
+
 /* closure = HorizontalScalarDiffusivity(nu, kappa) and HorizontalScalarBiharmonicDiffusivity(nu4, kappa4), both explicit with constant
  * coefficients, added to G^n of u, v and the tracers by ocn_hydro_calculate_tendencies / ocn_hydro_time_step; zeros switch a closure off */
 int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_t ntracers, const double* kappa, const double* kappa4) {
@@ -2830,6 +2919,7 @@ int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_
     ocn_set_error(ctx, "ocn_hydro_set_horizontal_closure: the %s closure reads %d halo cell(s) in x and y", bih ? "biharmonic" : "Laplacian", need);
     return OCN_EINVAL;
   }
+  hydro_clear_coefficient_tables(h);       // numbers again: the constant-coefficient instances, both formulations Horizontal
   h->kap2.assign(1 + (size_t)ntracers, 0.0);
   h->kap4.assign(1 + (size_t)ntracers, 0.0);
   h->kap2[0] = nu;
@@ -2843,6 +2933,104 @@ int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_
     h->kap4.clear();
   }
   return OCN_OK;
+}
+
+/* the formulation of the Laplacian-order (order 0) or biharmonic-order (order 1) viscous term: 0 Horizontal (delta and zeta fluxes), 1
+ * HorizontalDivergence (the delta fluxes alone); hyclosure_var.h.  After ocn_hydro_set_horizontal_closure, which resets both to 0, and
+ * before the setters that take a closure tuple */
+int ocn_hydro_set_horizontal_formulation(ocn_hydro* h, int32_t order, int32_t formulation) {
+  if (!h) return OCN_EINVAL;
+  if (order < 0 || order > 1 || formulation < 0 || formulation > 1) {
+    ocn_set_error(h->lg->ctx, "ocn_hydro_set_horizontal_formulation: order %d (0 Laplacian, 1 biharmonic) or formulation %d (0 Horizontal, "
+                  "1 HorizontalDivergence) out of range", (int)order, (int)formulation);
+    return OCN_EINVAL;
+  }
+  h->hform[order] = formulation;
+  return formulation ? hydro_constant_tables(h) : OCN_OK;
+}
+
+/* a coefficient that follows the grid: the two location tables of the viscosity (field 0) or of tracer q's diffusivity (field 1 + q) of
+ * the Laplacian-order (order 0) or biharmonic-order (order 1) closure, `nrows` x `nlevels` doubles each, entry [r + k * nrows] with r
+ * the row of the per-row metric arrays (nrows = Ny + 2 Hy + 1 of this grid or band) and k the level (nlevels = Nz).  a: nu at
+ * (Center, Center, Center) / kappa at (Face, Center, Center); b: nu at (Face, Face, Center) / kappa at (Center, Face, Center).
+ * Both null: back to the number of ocn_hydro_set_horizontal_closure.
+ * Entries that can reach the tendency of a cell the kernels write (rows j = 1 .. Ny of u, v and the tracers; reference row j is table
+ * row j - 1 + Hy) must be finite and >= 0:
+ *   nu a     rows j = 0 .. Ny      (delta at j - 1 and j of v's y flux, delta at j of u's x flux)
+ *   nu b     rows j = 1 .. Ny + 1  (zeta at j and j + 1 of u's y flux, zeta at j of v's x flux)
+ *   kappa a  rows j = 1 .. Ny      (the x fluxes of row j)
+ *   kappa b  rows j = 1 .. Ny + 1  (the y fluxes at faces j and j + 1)
+ * the other rows are never read. */
+int ocn_hydro_set_horizontal_coefficient_table(ocn_hydro* h, int32_t order, int32_t field, const double* a, const double* b, int32_t nrows,
+                                               int32_t nlevels) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const char* fn = "ocn_hydro_set_horizontal_coefficient_table";
+  const int nf = 1 + (int)h->c.size(), rows = g->N[1] + 2 * g->H[1] + 1, Ny = g->N[1], Hy = g->H[1];
+  if (order < 0 || order > 1 || field < 0 || field >= nf) {
+    ocn_set_error(ctx, "%s: order %d (0 Laplacian, 1 biharmonic) or field %d (0 the viscosity, 1 .. %d the tracers' diffusivities) out of range", fn,
+                  (int)order, (int)field, nf - 1);
+    return OCN_EINVAL;
+  }
+  if ((a == nullptr) != (b == nullptr)) {
+    ocn_set_error(ctx, "%s: one location table without the other", fn);
+    return OCN_EINVAL;
+  }
+  std::vector<ocn_hydro::CoefTab>& tabs = h->ctab[order];
+  if (!a) {
+    if ((size_t)field < tabs.size() && tabs[field].a) {
+      OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+      hipFree(tabs[field].a);
+      hipFree(tabs[field].b);
+      tabs[field] = ocn_hydro::CoefTab{};
+    }
+    return OCN_OK;
+  }
+  if (nrows != rows || nlevels != g->N[2]) {
+    ocn_set_error(ctx, "%s: tables of %d rows x %d levels given, this grid's are %d x %d (Ny + 2 Hy + 1 rows, Nz levels)", fn, (int)nrows,
+                  (int)nlevels, rows, g->N[2]);
+    return OCN_EINVAL;
+  }
+  const int need = order ? 2 : 1;        // required_halo_size, as for the numbers
+  if (g->H[0] < need || g->H[1] < need) {
+    ocn_set_error(ctx, "%s: the %s closure reads %d halo cell(s) in x and y", fn, order ? "biharmonic" : "Laplacian", need);
+    return OCN_EINVAL;
+  }
+  // reference rows [j0, j1] of each table that can reach a tendency (see above)
+  const int ja0 = field == 0 ? 0 : 1, ja1 = Ny, jb0 = 1, jb1 = Ny + 1;
+  for (int k = 0; k < g->N[2]; ++k) {
+    for (int which = 0; which < 2; ++which) {
+      const double* t = which ? b : a;
+      for (int j = which ? jb0 : ja0; j <= (which ? jb1 : ja1); ++j) {
+        const double x = t[(j - 1 + Hy) + (size_t)k * rows];
+        if (!(x >= 0) || !std::isfinite(x)) {
+          ocn_set_error(ctx, "%s: coefficients must be finite and >= 0: %g at row %d, level %d of the %s table (order %d, field %d)", fn, x, j,
+                        k + 1, which ? "second" : "first", (int)order, (int)field);
+          return OCN_EINVAL;
+        }
+      }
+    }
+  }
+  if (h->kap2.empty()) {
+    h->kap2.assign((size_t)nf, 0.0);
+    h->kap4.assign((size_t)nf, 0.0);
+  }
+  if (tabs.size() < (size_t)nf) tabs.resize(nf);
+  const size_t bytes = (size_t)rows * g->N[2] * sizeof(double);
+  OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));        // a step already queued may still read the previous values
+  if (!tabs[field].a) {
+    double *da = nullptr, *db = nullptr;
+    if (hipMalloc((void**)&da, bytes) != hipSuccess || hipMalloc((void**)&db, bytes) != hipSuccess) {
+      hipFree(da);
+      ocn_set_error(ctx, "allocation of %zu bytes failed", 2 * bytes);
+      return OCN_ENOMEM;
+    }
+    tabs[field] = ocn_hydro::CoefTab{da, db};
+  }
+  OCN_HIP_CHECK(ctx, hipMemcpy(tabs[field].a, a, bytes, hipMemcpyHostToDevice));
+  OCN_HIP_CHECK(ctx, hipMemcpy(tabs[field].b, b, bytes, hipMemcpyHostToDevice));
+  return hydro_constant_tables(h);
 }
 
 /* FluxBoundaryCondition on one side of u (field 0), v (field 1) or tracer q (field 2 + q), added to G^n after the interior terms
@@ -2890,6 +3078,38 @@ int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kin
   return OCN_OK;
 }
 
+// the positions of the explicit terms in a closure tuple (validated by the caller): slot 0 the Laplacian-order term (HorizontalScalar
+// or HorizontalDivergenceScalar), 1 the biharmonic-order term, 2 the variable vertical closure's; slots the tuple leaves out are zero
+// terms and go last.  Where the tuple holds both closures of one order, the HorizontalDivergence one is the momentum's term if that
+// formulation is set for the order (ocn_hydro_set_horizontal_formulation, called before) and the Horizontal one otherwise; the
+// tracers' term is always the Horizontal one (a HorizontalDivergence closure has no tracer flux)
+static void hydro_tuple_order(const ocn_hydro* h, int ntuple, const int32_t* tuple, int order[3], int order_c[3]) {
+  bool has[7] = {false, false, false, false, false, false, false};
+  for (int q = 0; q < ntuple; ++q) has[tuple[q]] = true;
+  for (int who = 0; who < 2; ++who) {
+    int* o = who ? order_c : order;
+    int n = 0;
+    for (int q = 0; q < ntuple; ++q) {
+      const int kind = tuple[q];
+      if (kind == OCN_CLOSURE_VERTICAL_SCALAR) continue;
+      const bool lap = kind == OCN_CLOSURE_HORIZONTAL_SCALAR || kind == OCN_CLOSURE_HORIZONTAL_DIVERGENCE_SCALAR;
+      const bool bih = kind == OCN_CLOSURE_HORIZONTAL_BIHARMONIC || kind == OCN_CLOSURE_HORIZONTAL_DIVERGENCE_BIHARMONIC;
+      const int slot = lap ? 0 : bih ? 1 : 2;
+      if (slot < 2) {
+        const int full = lap ? OCN_CLOSURE_HORIZONTAL_SCALAR : OCN_CLOSURE_HORIZONTAL_BIHARMONIC;
+        const int div = lap ? OCN_CLOSURE_HORIZONTAL_DIVERGENCE_SCALAR : OCN_CLOSURE_HORIZONTAL_DIVERGENCE_BIHARMONIC;
+        if (has[full] && has[div] && kind != (who == 0 && h->hform[slot] ? div : full)) continue;
+      }
+      o[n++] = slot;
+    }
+    for (int e = 0; e < 3; ++e) {        // slots the tuple leaves out: zero terms, last
+      bool in = false;
+      for (int q = 0; q < n; ++q) in = in || o[q] == e;
+      if (!in) o[n++] = e;
+    }
+  }
+}
+
 /* closure = ConvectiveAdjustmentVerticalDiffusivity(discretization; convective_kappaz, convective_nuz, background_kappaz,
  * background_nuz) (convective_adjustment_vertical_diffusivity.jl), alone or in a tuple; hyconvect.h */
 int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, double convective_kappaz, double convective_nuz,
@@ -2911,10 +3131,10 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
     return OCN_EINVAL;
   }
   // the kinds of the closure tuple in order (OCN_CLOSURE_*): the explicit terms are summed in that order
-  int order[3], n = 0, ncv = 0, seen[5] = {0, 0, 0, 0, 0};
+  int order[3], order_c[3], ncv = 0, seen[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int q = 0; q < ntuple; ++q) {
     const int kind = tuple[q];
-    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_RI_BASED) {
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_HORIZONTAL_DIVERGENCE_BIHARMONIC) {
       ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: unknown closure kind %d at tuple position %d", kind, q);
       return OCN_EINVAL;
     }
@@ -2929,17 +3149,12 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
       return OCN_EINVAL;
     }
     ncv += kind == OCN_CLOSURE_CONVECTIVE_ADJUSTMENT;
-    if (kind != OCN_CLOSURE_VERTICAL_SCALAR) order[n++] = kind == OCN_CLOSURE_HORIZONTAL_SCALAR ? 0 : kind == OCN_CLOSURE_HORIZONTAL_BIHARMONIC ? 1 : 2;
   }
   if (ntuple > 0 && ncv == 0) {
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure tuple holds no ConvectiveAdjustmentVerticalDiffusivity");
     return OCN_EINVAL;
   }
-  for (int e = 0; e < 3; ++e) {        // kinds the tuple leaves out: zero terms, last
-    bool in = false;
-    for (int q = 0; q < n; ++q) in = in || order[q] == e;
-    if (!in) order[n++] = e;
-  }
+  hydro_tuple_order(h, ntuple, tuple, order, order_c);
   const bool on = kc != 0.0 || nuc != 0.0 || kb != 0.0 || nub != 0.0;
   if (on && g->H[2] < 1) {
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure reads one halo cell in z (the grid has %d)", g->H[2]);
@@ -2966,7 +3181,7 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
   h->cv.nub = nub;
   h->cv.nzu = nuc != 0.0 || nub != 0.0;
   h->cv.nzc = kc != 0.0 || kb != 0.0;
-  for (int e = 0; e < 3; ++e) h->cv.order[e] = order[e];
+  for (int e = 0; e < 3; ++e) { h->cv.order[e] = order[e]; h->cv.order_c[e] = order_c[e]; }
   if (on) h->vk_last = OCN_CLOSURE_CONVECTIVE_ADJUSTMENT;
   return OCN_OK;
 }
@@ -3007,10 +3222,10 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
     ocn_set_error(ctx, "%s: a closure tuple of %d entries without its kinds", fn, (int)ntuple);
     return OCN_EINVAL;
   }
-  int order[3], n = 0, nrb = 0, seen[5] = {0, 0, 0, 0, 0};
+  int order[3], order_c[3], nrb = 0, seen[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int q = 0; q < ntuple; ++q) {
     const int kind = tuple[q];
-    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_RI_BASED) {
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_HORIZONTAL_DIVERGENCE_BIHARMONIC) {
       ocn_set_error(ctx, "%s: unknown closure kind %d at tuple position %d", fn, kind, q);
       return OCN_EINVAL;
     }
@@ -3024,17 +3239,12 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
       return OCN_EINVAL;
     }
     nrb += kind == OCN_CLOSURE_RI_BASED;
-    if (kind != OCN_CLOSURE_VERTICAL_SCALAR) order[n++] = kind == OCN_CLOSURE_HORIZONTAL_SCALAR ? 0 : kind == OCN_CLOSURE_HORIZONTAL_BIHARMONIC ? 1 : 2;
   }
   if (ntuple > 0 && nrb == 0) {
     ocn_set_error(ctx, "%s: the closure tuple holds no RiBasedVerticalDiffusivity", fn);
     return OCN_EINVAL;
   }
-  for (int e = 0; e < 3; ++e) {        // kinds the tuple leaves out: zero terms, last
-    bool in = false;
-    for (int q = 0; q < n; ++q) in = in || order[q] == e;
-    if (!in) order[n++] = e;
-  }
+  hydro_tuple_order(h, ntuple, tuple, order, order_c);
   const bool on = nu0 != 0.0 || kappa0 != 0.0;
   if (on && g->H[2] < 1) {
     ocn_set_error(ctx, "%s: the closure reads one halo cell in z (the grid has %d)", fn, g->H[2]);
@@ -3069,7 +3279,7 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
   rb.rp = HyRiParam{nu0, Ri0nu, Ridnu, kappa0, Ri0kappa, Ridkappa};
   rb.nzu = nu0 != 0.0;
   rb.nzc = kappa0 != 0.0;
-  for (int e = 0; e < 3; ++e) rb.order[e] = order[e];
+  for (int e = 0; e < 3; ++e) { rb.order[e] = order[e]; rb.order_c[e] = order_c[e]; }
   if (on) h->vk_last = OCN_CLOSURE_RI_BASED;
   return OCN_OK;
 }

@@ -446,30 +446,134 @@ def update_hydrostatic_pressure(pHY, buoyancy, tracers):
     check(pHY.lib.ocn_hydro_pressure(pHY.h, kind, g, al, be, T.h if T else None, S.h if S else None), pHY.grid.ctx.h)
 
 
+def _is_number(x):
+    return isinstance(x, (int, float, np.number)) and not isinstance(x, bool)
+
+
+def _positional_count(f):
+    """how many positional arguments f takes, or None where that cannot be told (a builtin, *args)"""
+    import inspect
+    try:
+        ps = list(inspect.signature(f).parameters.values())
+    except (TypeError, ValueError):
+        return None
+    if any(q.kind == q.VAR_POSITIONAL for q in ps):
+        return None
+    return sum(q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD) and q.default is q.empty for q in ps)
+
+
 class _ScalarClosure:
-    def __init__(self, nu=0.0, kappa=0.0):
-        self.nu = float(nu)
-        self.kappa = dict(kappa) if isinstance(kappa, dict) else float(kappa)
+    """nu and kappa (a value or {tracer: value}) of a scalar closure.  A value is a number or, for the horizontal closures, a function
+    whose result does not vary along x (both grids have a regular x, so neither a coefficient scaled with the grid spacing nor a
+    function of latitude / y and depth does):
+      * f(x, y, z) -- f(lambda, phi, z) on the sphere --, the continuous, time-independent form, evaluated once at the nodes of the
+        location the reference evaluates it at (closure_kernel_operators.jl:108-114): nu at (Center, Center, Center) for the delta
+        fluxes and at (Face, Face, Center) for the zeta fluxes, kappa at (Face, Center, Center) for the x flux and at
+        (Center, Face, Center) for the y flux;
+      * with discrete_form=True, f(i, j, k, grid, lx, ly, lz) -- f(..., parameters) with parameters=p --, the unlocalized
+        DiscreteDiffusionFunction without clock and fields (discrete_diffusion_function.jl:69-73): called once with broadcastable
+        1-based index arrays (j is the row of the whole grid on a latitude band), the grid and Center / Face; Δx, Δy, Δz and Az of this
+        module take the same arguments.
+    ValueError for what the library does not carry: array coefficients, localized discrete forms (loc=), functions
+    of time or of the model's fields, and anything but numbers on a VerticalScalarDiffusivity."""
+
+    FUNCTIONS = True
+
+    def __init__(self, nu=0.0, kappa=0.0, discrete_form=False, parameters=None, loc=None):
+        if loc is not None:
+            raise ValueError(f"{type(self).__name__}(loc={loc!r}): a localized discrete form is not available: the library evaluates an "
+                             "unlocalized function at each flux's own location")
+        self.discrete_form, self.parameters = bool(discrete_form), parameters
+        self.nu = self._coefficient(nu, "nu")
+        self.kappa = {n: self._coefficient(v, f"kappa[{n!r}]") for n, v in kappa.items()} if isinstance(kappa, dict) else \
+            self._coefficient(kappa, "kappa")
+
+    def _coefficient(self, value, what):
+        name = type(self).__name__
+        if _is_number(value):
+            return float(value)
+        if isinstance(value, (np.ndarray, list, tuple)) or hasattr(value, "__array__"):
+            raise ValueError(f"{name}({what}=array): AbstractArray coefficients are not available: a coefficient is a number or a zonally "
+                             "uniform function, held as a (row, level) table")
+        if not callable(value):
+            raise ValueError(f"{name}({what}={value!r}): a number or a function")
+        if not self.FUNCTIONS:
+            raise ValueError(f"{name}({what}=function): this closure takes numbers only (its solve's coefficients are one per field)")
+        n, want = _positional_count(value), (7 + (self.parameters is not None) if self.discrete_form else 3)
+        if n is not None and n != want:
+            form = "f(i, j, k, grid, lx, ly, lz" + (", parameters)" if self.parameters is not None else ")") if self.discrete_form else "f(x, y, z)"
+            raise ValueError(f"{name}({what}=function of {n} arguments): the coefficient is {form}, evaluated once; functions of time "
+                             "(f(x, y, z, t)) or of the clock and the model's fields are not available")
+        return value
 
     def kappa_of(self, name):
-        return float(self.kappa.get(name, 0.0)) if isinstance(self.kappa, dict) else self.kappa
+        return self.kappa.get(name, 0.0) if isinstance(self.kappa, dict) else self.kappa
+
+    def coefficients(self, names):
+        """[nu, kappa of each tracer in names]"""
+        return [self.nu] + [self.kappa_of(n) for n in names]
 
     def __repr__(self):
-        return f"{type(self).__name__}(nu={self.nu!r}, kappa={self.kappa!r})"
+        show = lambda v: v if _is_number(v) else getattr(v, "__name__", type(v).__name__)                    # noqa: E731
+        kappa = {n: show(v) for n, v in self.kappa.items()} if isinstance(self.kappa, dict) else show(self.kappa)
+        extra = (", discrete_form=True" + (f", parameters={self.parameters!r}" if self.parameters is not None else "")) if self.discrete_form else ""
+        return f"{type(self).__name__}(nu={show(self.nu)!r}, kappa={kappa!r}{extra})"
 
 
 class HorizontalScalarDiffusivity(_ScalarClosure):
-    """HorizontalScalarDiffusivity(nu, kappa): explicit horizontal Laplacian viscosity and diffusivity, constant coefficients
-    (TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl:101); kappa a number or {tracer: value}"""
+    """HorizontalScalarDiffusivity(nu, kappa): explicit horizontal Laplacian viscosity and diffusivity
+    (TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl:101); kappa a value or {tracer: value}; values are
+    numbers or zonally uniform functions (see _ScalarClosure)"""
 
 
 class HorizontalScalarBiharmonicDiffusivity(_ScalarClosure):
-    """HorizontalScalarBiharmonicDiffusivity(nu, kappa): explicit horizontal biharmonic viscosity and diffusivity [m^4/s], constant
-    coefficients (scalar_biharmonic_diffusivity.jl:21); needs 2 halo cells in x and y"""
+    """HorizontalScalarBiharmonicDiffusivity(nu, kappa): explicit horizontal biharmonic viscosity and diffusivity [m^4/s]
+    (scalar_biharmonic_diffusivity.jl:21); needs 2 halo cells in x and y; values as for HorizontalScalarDiffusivity"""
+
+
+class _DivergenceClosure(_ScalarClosure):
+    def __init__(self, nu=0.0, kappa=0.0, **kw):
+        if not (_is_number(kappa) and kappa == 0) and not (isinstance(kappa, dict) and all(_is_number(v) and v == 0 for v in kappa.values())):
+            raise ValueError(f"{type(self).__name__}(kappa={kappa!r}): the HorizontalDivergence formulation has no tracer flux (the "
+                             "reference would silently apply nothing): give kappa to a HorizontalScalar(Biharmonic)Diffusivity")
+        super().__init__(nu, 0.0, **kw)
+
+
+class HorizontalDivergenceScalarDiffusivity(_DivergenceClosure):
+    """HorizontalDivergenceScalarDiffusivity(nu): divergence damping, flux_ux = flux_vy = -nu delta and every other flux zero
+    (scalar_diffusivity.jl with HorizontalDivergenceFormulation, abstract_scalar_diffusivity_closure.jl:194-196); nu as for
+    HorizontalScalarDiffusivity; kappa must be 0"""
+
+
+class HorizontalDivergenceScalarBiharmonicDiffusivity(_DivergenceClosure):
+    """HorizontalDivergenceScalarBiharmonicDiffusivity(nu): biharmonic divergence damping, flux_ux = flux_vy = +nu delta* and every
+    other flux zero (abstract_scalar_biharmonic_diffusivity_closure.jl:56-57); needs 2 halo cells in x and y; kappa must be 0"""
 
 
 class VerticalScalarDiffusivity(_ScalarClosure):
-    """VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): the implicit vertical solve inside ab2_step!"""
+    """VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa): the implicit vertical solve inside ab2_step!;
+    numbers only"""
+
+    FUNCTIONS = False
+
+
+def _metric_operator(rowwise, levelwise=None):
+    """Δx, Δy, Az or Δz at (i, j, k) of location (lx, ly, lz) from the grid's per-row and per-level arrays (halo rows included); j is the
+    row of the whole grid, as the discrete form passes it"""
+    def op(i, j, k, grid, lx, ly, lz):
+        if levelwise is not None:
+            a = levelwise(grid, lz)
+            return a[np.asarray(k) - 1] + 0.0 * (np.asarray(i) + np.asarray(j))
+        a = rowwise(grid, lx, ly)
+        return a[np.asarray(j) - 1 + grid.Hy - grid.j0] + 0.0 * (np.asarray(i) + np.asarray(k))
+    return op
+
+
+# regular x: Δx^cc = Δx^fc, Δx^ff = Δx^cf, Δy^cc = Δy^fc, Δy^ff = Δy^cf, Az^fc = Az^cc, Az^cf = Az^ff (the kernels' own identities)
+Δx = _metric_operator(lambda g, lx, ly: g.Δxᶠᶜᵃ if ly == Center else g.Δxᶜᶠᵃ)
+Δy = _metric_operator(lambda g, lx, ly: g.Δyᶠᶜᵃ if ly == Center else g.Δyᶜᶠᵃ)
+Az = _metric_operator(lambda g, lx, ly: g.Azᶜᶜᵃ if ly == Center else g.metric(11))
+Δz = _metric_operator(None, lambda g, lz: g.Δzᵃᵃᶜ if lz == Center else g.Δzᵃᵃᶠ)
 
 
 class ConvectiveAdjustmentVerticalDiffusivity:
@@ -525,9 +629,18 @@ class RiBasedVerticalDiffusivity:
 
 
 _CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
-                  ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity)
+                  ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, HorizontalDivergenceScalarDiffusivity,
+                  HorizontalDivergenceScalarBiharmonicDiffusivity)
 _KIND_CODE = {VerticalScalarDiffusivity: 0, HorizontalScalarDiffusivity: 1, HorizontalScalarBiharmonicDiffusivity: 2,
-              ConvectiveAdjustmentVerticalDiffusivity: 3, RiBasedVerticalDiffusivity: 4}      # OCN_CLOSURE_*
+              ConvectiveAdjustmentVerticalDiffusivity: 3, RiBasedVerticalDiffusivity: 4, HorizontalDivergenceScalarDiffusivity: 5,
+              HorizontalDivergenceScalarBiharmonicDiffusivity: 6}      # OCN_CLOSURE_*
+# the closures of each order of the three-slot sum (Laplacian-order term, biharmonic-order term): the Horizontal one, the Divergence one
+_ORDERS = ((HorizontalScalarDiffusivity, HorizontalDivergenceScalarDiffusivity),
+           (HorizontalScalarBiharmonicDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity))
+
+
+def _nonzero(value):
+    return not _is_number(value) or value != 0
 
 
 def closure_parts(closure):
@@ -547,6 +660,11 @@ def closure_parts(closure):
         if kind in parts:
             raise ValueError(f"a closure tuple holds at most one {kind.__name__}")
         parts[kind] = c
+    # one term of each order per field: the explicit terms are a three-slot sum (Laplacian order, biharmonic order, vertical)
+    for full, div in _ORDERS:
+        if full in parts and div in parts and _nonzero(parts[full].nu) and _nonzero(parts[div].nu):
+            raise ValueError(f"{full.__name__} and {div.__name__} both with a non-zero nu: a closure tuple holds at most one momentum term "
+                             "of each order")
     return parts
 
 
@@ -741,11 +859,47 @@ class HydrostaticState:
                                                  0 if arr is None else arr.size), self.grid.ctx.h)
         self.boundary_conditions = bcs
 
+    def _coefficient_tables(self, closure, f, is_nu, what):
+        """the two (rows, Nz) location tables of the function coefficient f of `closure`: rows are those of the grid's per-row metric
+        arrays (reference row j at j - 1 + Hy, halo rows included; the band's own rows on a latitude band), levels 1 .. Nz"""
+        g = self.grid
+        rows = g.Ny + 2 * g.Hy + 1
+        out = []
+        for lx, ly in (((Center, Center), (Face, Face)) if is_nu else ((Face, Center), (Center, Face))):
+            with np.errstate(all="ignore"):          # rows beyond the last halo row hold no node or metric and are never read
+                if closure.discrete_form:
+                    i = np.arange(1, g.Nx + 1).reshape(-1, 1, 1)
+                    j = (np.arange(rows) + 1 - g.Hy + g.j0).reshape(1, -1, 1)
+                    k = np.arange(1, g.Nz + 1).reshape(1, 1, -1)
+                    extra = () if closure.parameters is None else (closure.parameters,)
+                    val = f(i, j, k, g, lx, ly, Center, *extra)
+                else:
+                    y = np.full(rows, np.nan)
+                    nodes = g.metric(8 if ly == Face else 9)[:rows]
+                    y[:nodes.size] = nodes
+                    val = f(g.nodes(lx, 0)[:g.Nx].reshape(-1, 1, 1), y.reshape(1, -1, 1), g.znodes(Center).reshape(1, 1, -1))
+            val = np.asarray(val, dtype=np.float64)
+            try:
+                shape = np.broadcast_shapes(val.shape, (1, rows, g.Nz))
+            except ValueError:
+                shape = ()
+            if len(shape) != 3 or shape[0] not in (1, g.Nx):
+                raise ValueError(f"{what}: the function's result of shape {val.shape} does not broadcast over the ({g.Nx}, {rows}, {g.Nz}) "
+                                 "points it was called with")
+            val = np.broadcast_to(val, shape)
+            if not np.array_equal(val, np.broadcast_to(val[:1], shape), equal_nan=True):
+                raise ValueError(f"{what}: the coefficient varies along x; the library carries zonally uniform coefficients only (a "
+                                 "(row, level) table per location: a function of y / latitude and depth, or of the grid spacings)")
+            out.append(np.asfortranarray(val[0]))
+        return tuple(out)
+
     def set_closure(self, closure):
         """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one
         closure object | a tuple of them (at most one of each kind): HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
-        VerticalScalarDiffusivity, ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity (at most one of the last two);
-        explicit terms summed in tuple order"""
+        HorizontalDivergenceScalarDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
+        ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity (at most one of the last two; at most one non-zero nu among
+        the two closures of the Laplacian order and among the two of the biharmonic order); explicit terms summed in tuple order.
+        Function coefficients are evaluated here, once; `horizontal_coefficient_tables` keeps what was sent"""
         parts = closure_parts(closure)
         names = list(self.tracers)
         PD = C.POINTER(C.c_double)
@@ -754,10 +908,29 @@ class HydrostaticState:
         def coeffs(kind):
             c = parts.get(kind, zero)
             return c.nu, np.array([c.kappa_of(n) for n in names] or [0.0])
-        nu2, k2 = coeffs(HorizontalScalarDiffusivity)
-        nu4, k4 = coeffs(HorizontalScalarBiharmonicDiffusivity)
-        check(self.lib.ocn_hydro_set_horizontal_closure(self.h, nu2, nu4, len(names), k2.ctypes.data_as(PD), k4.ctypes.data_as(PD)),
+        # per order of the horizontal closures: the numbers (0 where a table stands in), the formulation, the tables of the functions
+        numbers, forms, tables = [], [], {}
+        for order, (full, div) in zip(("laplacian", "biharmonic"), _ORDERS):
+            cf, cd = parts.get(full, zero), parts.get(div, zero)
+            cnu = cd if _nonzero(cd.nu) else cf
+            forms.append(int(cnu is cd and cd is not zero))
+            values = []
+            for c, field, value in [(cnu, "nu", cnu.nu)] + [(cf, n, cf.kappa_of(n)) for n in names]:
+                if not _is_number(value):
+                    tables[order, field] = self._coefficient_tables(c, value, field == "nu", f"{type(c).__name__}, {field}")
+                values.append(value if _is_number(value) else 0.0)
+            numbers.append(np.array(values + [0.0]))
+        (n2, n4) = numbers
+        check(self.lib.ocn_hydro_set_horizontal_closure(self.h, n2[0], n4[0], len(names), n2[1:].ctypes.data_as(PD), n4[1:].ctypes.data_as(PD)),
               self.grid.ctx.h)
+        self.horizontal_coefficient_tables = {}
+        for o, form in enumerate(forms):
+            check(self.lib.ocn_hydro_set_horizontal_formulation(self.h, o, form), self.grid.ctx.h)
+        for (order, field), (a, b) in tables.items():
+            check(self.lib.ocn_hydro_set_horizontal_coefficient_table(self.h, ("laplacian", "biharmonic").index(order), (["nu"] + names).index(field),
+                                                                      a.ctypes.data_as(PD), b.ctypes.data_as(PD), a.shape[0], a.shape[1]),
+                  self.grid.ctx.h)
+            self.horizontal_coefficient_tables[order, field] = (a, b)
         nu, k = coeffs(VerticalScalarDiffusivity)
         check(self.lib.ocn_hydro_set_closure(self.h, nu, len(names), k.ctypes.data_as(PD)), self.grid.ctx.h)
         def kinds_of(kind):

@@ -431,6 +431,27 @@ int ocn_hydro_set_closure(ocn_hydro* h, double nu, int32_t ntracers, const doubl
  * Zeros (the default) switch a closure off and launch nothing.  OCN_EINVAL for a negative or NaN coefficient, an ntracers that is
  * not the handle's, a Laplacian coefficient with fewer than 1 halo cell in x or y, a biharmonic one with fewer than 2. */
 int ocn_hydro_set_horizontal_closure(ocn_hydro* h, double nu, double nu4, int32_t ntracers, const double* kappa, const double* kappa4);
+/* Coefficients of the two closures above that follow the grid, and their HorizontalDivergence formulations (hyclosure_var.h).
+ * ocn_hydro_set_horizontal_closure with numbers keeps its meaning: it removes every table and sets both formulations back to 0.
+ *
+ * ocn_hydro_set_horizontal_formulation: the viscous term of the Laplacian-order (order 0) or biharmonic-order (order 1) closure is the
+ * Horizontal one (formulation 0: flux_ux = flux_vy = -/+ nu delta, flux_uy = -flux_vx = +/- nu zeta) or the HorizontalDivergence one
+ * (formulation 1, HorizontalDivergenceScalarDiffusivity / HorizontalDivergenceScalarBiharmonicDiffusivity: the delta fluxes alone,
+ * abstract_scalar_diffusivity_closure.jl:194-196, abstract_scalar_biharmonic_diffusivity_closure.jl:56-57; no tracer flux).  Call it
+ * before a setter that takes a closure tuple.  OCN_EINVAL outside 0 / 1.
+ *
+ * ocn_hydro_set_horizontal_coefficient_table: the coefficient `field` (0 the viscosity, 1 + q the diffusivity of tracer q) of the
+ * closure of `order` is zonally uniform and varies with row and level: two tables of nrows x nlevels doubles, entry [r + k * nrows],
+ * r the row of the grid's per-row metric arrays (reference row j is r = j - 1 + Hy; nrows = Ny + 2 Hy + 1 of this grid or band) and
+ * k = 0 .. Nz - 1 (nlevels = Nz).  `a` holds the coefficient where the reference evaluates it for the first kind of flux, `b` for the
+ * second (closure_kernel_operators.jl:108-125): nu at (Center, Center, Center) for the delta fluxes and at (Face, Face, Center) for
+ * the zeta fluxes; kappa at (Face, Center, Center) for the x flux and at (Center, Face, Center) for the y flux.  a = b = NULL returns
+ * the field to its number.  The field is on while it has tables, whatever its number.  OCN_EINVAL for an order or field out of
+ * range, one table without the other, a shape that is not the grid's, too small a halo (1 cell, biharmonic 2), or an entry in a row
+ * that can reach a tendency (listed at the definition) that is negative, NaN or infinite. */
+int ocn_hydro_set_horizontal_formulation(ocn_hydro* h, int32_t order, int32_t formulation);
+int ocn_hydro_set_horizontal_coefficient_table(ocn_hydro* h, int32_t order, int32_t field, const double* a, const double* b, int32_t nrows,
+                                               int32_t nlevels);
 /* FluxBoundaryCondition on one side (OCN_WEST .. OCN_TOP) of u (field 0), v (field 1) or tracer q (field 2 + q), applied to G^n after
  * the interior tendencies by ocn_hydro_calculate_tendencies / ocn_hydro_time_step (apply_flux_bcs.jl).  kind 0: none (default);
  * 1: the constant `value`; 2: `n` values at `host` (z sides Nx x Ny, x sides Ny x Nz, y sides Nx x Nz of this grid or band,
@@ -453,7 +474,10 @@ int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kin
  * v gets the interior-face w-shear term -d_z(Az (-nu d_x w)) / V (d_y w for v) whenever a viscosity is non-zero.  discretization 1,
  * explicit: G^n gets -div(-K d_z f) for u, v and the tracers.  The explicit terms are summed with those of
  * ocn_hydro_set_horizontal_closure in the order of the closure tuple: `tuple` lists the kinds of its `ntuple` closures in order
- * (OCN_CLOSURE_*, each at most once; ntuple 0: this closure alone or in front).  All-zero coefficients (the default) switch it off.
+ * (OCN_CLOSURE_*, each at most once; ntuple 0: this closure alone or in front).  A tuple may hold the Horizontal and the
+ * HorizontalDivergence closure of one order (kinds 1 and 5, 2 and 6) when at most one of them has a non-zero viscosity: the momentum's
+ * term of that order then stands where the closure with the formulation of ocn_hydro_set_horizontal_formulation stands, the tracers'
+ * where the Horizontal one does.  All-zero coefficients (the default) switch it off.
  * OCN_EINVAL for a negative, NaN or infinite coefficient, a discretization other than 0 / 1, a grid without a halo cell in z, a tuple
  * with a kind twice (a second convective adjustment) or without this closure. */
 enum {
@@ -461,7 +485,9 @@ enum {
   OCN_CLOSURE_HORIZONTAL_SCALAR = 1,        /* HorizontalScalarDiffusivity */
   OCN_CLOSURE_HORIZONTAL_BIHARMONIC = 2,    /* HorizontalScalarBiharmonicDiffusivity */
   OCN_CLOSURE_CONVECTIVE_ADJUSTMENT = 3,    /* ConvectiveAdjustmentVerticalDiffusivity */
-  OCN_CLOSURE_RI_BASED = 4                  /* RiBasedVerticalDiffusivity */
+  OCN_CLOSURE_RI_BASED = 4,                 /* RiBasedVerticalDiffusivity */
+  OCN_CLOSURE_HORIZONTAL_DIVERGENCE_SCALAR = 5,      /* HorizontalDivergenceScalarDiffusivity: the Laplacian-order term of u and v */
+  OCN_CLOSURE_HORIZONTAL_DIVERGENCE_BIHARMONIC = 6   /* HorizontalDivergenceScalarBiharmonicDiffusivity: their biharmonic-order term */
 };
 int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, double convective_kappaz, double convective_nuz,
                                         double background_kappaz, double background_nuz, int32_t ntuple, const int32_t* tuple);
