@@ -1082,6 +1082,8 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 
 // RiBasedVerticalDiffusivity: k_hy_ri_diff (its solve and explicit terms: hyconvect.h / hyclosure.h with the Center-location variants)
 #include "hyribased.h"
+// IsopycnalSkewSymmetricDiffusivity: the slope pass of update_state!, the flux pass of calculate_tendencies!, the solve's coefficients
+#include "hyisopycnal.h"
 
 // the implicit free surface (ImplicitFreeSurface with the PCG solver)
 #include "hyimplicit.h"
@@ -1330,6 +1332,20 @@ struct ocn_hydro {
     HyRiParam rp{};
   } cv, rb;
   int vk_last = 0;                           // the closure (OCN_CLOSURE_*) whose fields ocn_hydro_diffusivity_field returns
+  // IsopycnalSkewSymmetricDiffusivity (hyisopycnal.h), vertically implicit: per-tracer kappa_symmetric / kappa_skew, the stored fields
+  // (eps_R33 a field of the handle, eps, R13, R23, R31, R32 plain arrays of its parent shape), the coefficient arrays of the tracers'
+  // solves (one per distinct kappa_symmetric; kzi[q] the array of tracer q) and the solve's scratch
+  struct Iso {
+    bool on = false;
+    HyIsoParam p{0.0, 0.0};
+    double dzf_top = 0.0;                    // dz^f at face Nz + 2
+    std::vector<double> ks, kk;
+    ocn_hfield* er33 = nullptr;
+    double* w[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<double*> kz;
+    std::vector<int> kzi;
+    double* t = nullptr;
+  } iso;
 };
 
 static HyGrid hy_grid(const ocn_hgrid* g) {
@@ -1503,10 +1519,40 @@ static void hydro_rb_diffusivities(ocn_hydro* h) {
 }
 // the variable-coefficient vertical closure that is on (CAVD or RBVD, never both), or null
 static const ocn_hydro::Cavd* hydro_vk(const ocn_hydro* h) { return h->cv.on ? &h->cv : h->rb.on ? &h->rb : nullptr; }
-// the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient
+// the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient;
+// an IsopycnalSkewSymmetricDiffusivity always solves the tracers (and never u or v: its viscosity is zero)
 static bool hydro_cv_implicit_uv(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->disc == 0 && v->nzu; }
-static bool hydro_cv_implicit_c(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->disc == 0 && v->nzc; }
+static bool hydro_cv_implicit_c(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return h->iso.on || (v && v->disc == 0 && v->nzc); }
+static HyMetric hy_metric(const ocn_hgrid* g);
+// (Center, Center, Center) coefficients: a RiBasedVerticalDiffusivity at Center (never together with the isopycnal closure)
+static bool hydro_cv_center(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->loc == 1; }
+// calculate_diffusivities! of the IsopycnalSkewSymmetricDiffusivity (hyisopycnal.h): the slope pass over the interior plus one column
+// and row, the x / y fills of eps_R33 (no condition in z, as for any (Center, Center, Face) diffusivity field), then the coefficient
+// arrays of the tracers' solves -- after the CAVD / RBVD pass, whose kappa they add
+static void hydro_iso_diffusivities(ocn_hydro* h) {
+  const ocn_hgrid* g = h->lg;
+  ocn_hydro::Iso& s = h->iso;
+  const ocn_hfield *K = s.er33, *T = h->c[h->bT], *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  const long syk = K->T[0], szk = (long)K->T[0] * K->T[1];
+  ocn_launch(k_hy_iso_slopes, dim3((g->N[0] + 1 + 63) / 64, (g->N[1] + 1 + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, hy_metric(g), h->buoy, s.p,
+             s.dzf_top, (const double*)T->d, S ? (const double*)S->d : (const double*)nullptr, s.w[0], s.w[1], s.w[2], s.w[3], s.w[4], K->d,
+             (long)T->T[0], (long)T->T[0] * T->T[1], syk, szk);
+  hfield_fill(s.er33, false);
+  const ocn_hydro::Cavd* v = hydro_vk(h);
+  const double* vk = v && v->disc == 0 && v->nzc ? (const double*)v->kap->d : (const double*)nullptr;
+  for (size_t e = 0; e < s.kz.size(); ++e) {
+    double ks = 0.0;
+    for (size_t q = 0; q < s.kzi.size(); ++q)
+      if (s.kzi[q] == (int)e) ks = s.ks[q];
+    ocn_launch(k_hy_iso_kz, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]), dim3(64, 4, 1), g->ctx->stream, g->N[0], g->N[1], g->N[2],
+               g->H[0], g->H[1], g->H[2], ks, (const double*)K->d, vk, s.kz[e], syk, szk);
+  }
+}
 static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of h->kap (0 u / v, 1 + n tracer n)
+  if (h->iso.on && q > 0) {
+    const ocn_hfield* K = h->iso.er33;
+    return HyCvSolve{h->iso.kz[h->iso.kzi[q - 1]], (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->iso.t};
+  }
   const ocn_hydro::Cavd* v = hydro_vk(h);
   const ocn_hfield* K = q == 0 ? v->nu : v->kap;
   return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, v->t};
@@ -1518,7 +1564,7 @@ static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q
   hy_cols(g, b, gr);
   const HyCvSolve s = hydro_cv_solve(h, q);
   const long sy = f->T[0], sz = (long)f->T[0] * f->T[1];
-  loc += hydro_vk(h)->loc == 1 ? 3 : 0;
+  loc += hydro_cv_center(h) ? 3 : 0;
   if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 1) ocn_launch(k_hy_cv_implicit<1>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 2) ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
@@ -1535,6 +1581,7 @@ static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   hy_w_launch(h->u, h->v, h->w);
   if (h->cv.on) hydro_cv_diffusivities(h);
   if (h->rb.on) hydro_rb_diffusivities(h);
+  if (h->iso.on) hydro_iso_diffusivities(h);
   if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, h->bT >= 0 ? h->c[h->bT] : nullptr, h->bS >= 0 ? h->c[h->bS] : nullptr);
   hfield_fill(h->w);
   hfield_fill(h->pHY);
@@ -1743,6 +1790,32 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
                (long)c->T[0] * c->T[1], HyCvTerm{});
     if (lap && bih) { HY_CLO_C(true, true) } else if (lap) { HY_CLO_C(true, false) } else { HY_CLO_C(false, true) }
 #undef HY_CLO_C
+  }
+}
+
+// the IsopycnalSkewSymmetricDiffusivity's explicit fluxes (hyisopycnal.h): G_c <- G_c - div q for every tracer, one launch per
+// HY_ISO_MAXT tracers, a tracer whose two kappas are zero included (the reference subtracts eps * 0 from its tendency, which is NaN
+// where eps is NaN); nothing is launched while the closure is off
+static void hydro_iso_fluxes(ocn_hydro* h) {
+  const ocn_hydro::Iso& s = h->iso;
+  if (!s.on) return;
+  const ocn_hgrid* g = h->lg;
+  const ocn_hfield* K = s.er33;
+  const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
+  for (size_t q0 = 0; q0 < h->c.size(); q0 += HY_ISO_MAXT) {
+    HyIsoTracers tr;
+    tr.n = 0;
+    for (size_t q = q0; q < h->c.size() && q < q0 + HY_ISO_MAXT; ++q) {
+      tr.c[tr.n] = h->c[q]->d;
+      tr.G[tr.n] = h->gn[2 + q]->d;
+      tr.ks[tr.n] = s.ks[q];
+      tr.kk[tr.n] = s.kk[q];
+      ++tr.n;
+    }
+    if (!tr.n) continue;
+    const ocn_hfield* c = h->c[q0];
+    ocn_launch(k_hy_iso_flux, gr, b, g->ctx->stream, hy_metric(g), tr, (const double*)s.w[0], (const double*)s.w[1], (const double*)s.w[2],
+               (const double*)s.w[3], (const double*)s.w[4], (long)c->T[0], (long)c->T[0] * c->T[1], (long)K->T[0], (long)K->T[0] * K->T[1]);
   }
 }
 
@@ -2010,7 +2083,7 @@ static int hydro_fused_tracers(ocn_hydro* h, double dt, double chi, bool* pressu
         dim3 b2, g2;
         hy_cols(g, b2, g2);
         ocn_hfield* f = h->c[q];
-        if (hydro_vk(h)->loc == 1)
+        if (hydro_cv_center(h))
           ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
                      hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
         else
@@ -2721,6 +2794,18 @@ int ocn_hydro_create_implicit(const ocn_hydro_desc* d, ocn_ifs* free_surface, oc
   return hydro_create(d, nullptr, free_surface, out);
 }
 
+static void hydro_iso_release(ocn_hydro* h) {
+  ocn_hydro::Iso& s = h->iso;
+  if (s.er33) ocn_hfield_destroy(s.er33);
+  s.er33 = nullptr;
+  for (double*& p : s.w) { hipFree(p); p = nullptr; }
+  for (double* p : s.kz) hipFree(p);
+  s.kz.clear();
+  s.kzi.clear();
+  hipFree(s.t);
+  s.t = nullptr;
+  s.on = false;
+}
 void ocn_hydro_destroy(ocn_hydro* h) {
   if (!h) return;
   ocn_hgrid* g = h->lg;
@@ -2740,6 +2825,7 @@ void ocn_hydro_destroy(ocn_hydro* h) {
     if (v->nu) ocn_hfield_destroy(v->nu);
     hipFree(v->t);
   }
+  hydro_iso_release(h);
   delete h;
   hgrid_release(g);
 }
@@ -3160,6 +3246,11 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: the closure reads one halo cell in z (the grid has %d)", g->H[2]);
     return OCN_EINVAL;
   }
+  if (on && h->iso.on && discretization == 1) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: an IsopycnalSkewSymmetricDiffusivity is on: next to it the closure is vertically "
+                  "implicit (the explicit form is not carried in one tuple with it)");
+    return OCN_EUNSUPPORTED;
+  }
   if (on && h->rb.on) {
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a RiBasedVerticalDiffusivity is on (at most one variable-coefficient vertical closure)");
     return OCN_EINVAL;
@@ -3250,6 +3341,12 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
     ocn_set_error(ctx, "%s: the closure reads one halo cell in z (the grid has %d)", fn, g->H[2]);
     return OCN_EINVAL;
   }
+  if (on && h->iso.on && (discretization == 1 || location == 1)) {
+    ocn_set_error(ctx, "%s: an IsopycnalSkewSymmetricDiffusivity is on: next to it the closure is vertically implicit with its coefficients at "
+                  "Face (the Center location's solve interpolates cell-centred coefficients, another column type; the explicit form is not "
+                  "carried in one tuple with it)", fn);
+    return OCN_EUNSUPPORTED;
+  }
   if (on && h->cv.on) {
     ocn_set_error(ctx, "%s: a ConvectiveAdjustmentVerticalDiffusivity is on (at most one variable-coefficient vertical closure)", fn);
     return OCN_EINVAL;
@@ -3291,6 +3388,138 @@ ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which) {
   if (!h || which < 0 || which > 1) return nullptr;
   const ocn_hydro::Cavd& v = h->vk_last == OCN_CLOSURE_RI_BASED ? h->rb : h->cv;
   return which == 0 ? v.kap : v.nu;
+}
+
+/* closure = IsopycnalSkewSymmetricDiffusivity(VerticallyImplicitTimeDiscretization(); kappa_skew, kappa_symmetric, slope_limiter =
+ * FluxTapering(max_slope), isopycnal_tensor = SmallSlopeIsopycnalTensor(minimum_bz)) (isopycnal_skew_symmetric_diffusivity.jl), alone
+ * or in a tuple; hyisopycnal.h */
+int ocn_hydro_set_isopycnal_diffusivity(ocn_hydro* h, int32_t discretization, double max_slope, double minimum_bz, int32_t ntracers,
+                                        const double* kappa_skew, const double* kappa_symmetric, int32_t ntuple, const int32_t* tuple) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const char* fn = "ocn_hydro_set_isopycnal_diffusivity";
+  if (discretization == 1) {
+    ocn_set_error(ctx, "%s: ExplicitTimeDiscretization cannot run in the reference either (explicit_kappa_dz_c's explicit method takes 9 arguments "
+                  "and is called with 10: a MethodError); only the vertically implicit form (0) exists", fn);
+    return OCN_EUNSUPPORTED;
+  }
+  if (discretization != 0) {
+    ocn_set_error(ctx, "%s: discretization 0 (vertically implicit), got %d", fn, (int)discretization);
+    return OCN_EINVAL;
+  }
+  if (ntracers != (int)h->c.size() || (ntracers > 0 && (!kappa_skew || !kappa_symmetric))) {
+    ocn_set_error(ctx, "%s: kappa_skew and kappa_symmetric hold one number per tracer of the model (%d), got %d", fn, (int)h->c.size(), (int)ntracers);
+    return OCN_EINVAL;
+  }
+  bool on = false;
+  for (int q = 0; q < ntracers; ++q) {
+    if (!(kappa_skew[q] >= 0 && kappa_symmetric[q] >= 0) || !std::isfinite(kappa_skew[q]) || !std::isfinite(kappa_symmetric[q])) {
+      ocn_set_error(ctx, "%s: kappa_skew and kappa_symmetric must be finite and >= 0 (tracer %d: %g, %g)", fn, q, kappa_skew[q], kappa_symmetric[q]);
+      return OCN_EINVAL;
+    }
+    on = on || kappa_skew[q] != 0.0 || kappa_symmetric[q] != 0.0;
+  }
+  if (!(max_slope >= 0) || !std::isfinite(max_slope)) {
+    ocn_set_error(ctx, "%s: max_slope must be finite and >= 0 (%g)", fn, max_slope);
+    return OCN_EINVAL;
+  }
+  if (!(minimum_bz >= 0) || !std::isfinite(minimum_bz)) {
+    ocn_set_error(ctx, "%s: minimum_bz must be finite and >= 0 (%g)", fn, minimum_bz);
+    return OCN_EINVAL;
+  }
+  if (ntuple < 0 || (ntuple > 0 && !tuple)) {
+    ocn_set_error(ctx, "%s: a closure tuple of %d entries without its kinds", fn, (int)ntuple);
+    return OCN_EINVAL;
+  }
+  int niso = 0;
+  for (int q = 0; q < ntuple; ++q) {
+    const int kind = tuple[q];
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_ISOPYCNAL_SKEW_SYMMETRIC) {
+      ocn_set_error(ctx, "%s: unknown closure kind %d at tuple position %d", fn, kind, q);
+      return OCN_EINVAL;
+    }
+    niso += kind == OCN_CLOSURE_ISOPYCNAL_SKEW_SYMMETRIC;
+  }
+  if (niso > 1) {
+    ocn_set_error(ctx, "%s: a closure tuple holds at most one IsopycnalSkewSymmetricDiffusivity (one set of slope fields per model)", fn);
+    return OCN_EINVAL;
+  }
+  if (ntuple > 0 && niso == 0) {
+    ocn_set_error(ctx, "%s: the closure tuple holds no IsopycnalSkewSymmetricDiffusivity", fn);
+    return OCN_EINVAL;
+  }
+  if (!on) {
+    hipStreamSynchronize(ctx->stream);
+    hydro_iso_release(h);
+    return OCN_OK;
+  }
+  if (h->buoy.kind == 0 || h->bT < 0) {
+    ocn_set_error(ctx, "%s: the model has no buoyancy: every slope would be 0 / 0", fn);
+    return OCN_EUNSUPPORTED;
+  }
+  if (g->H[0] < 2 || g->H[1] < 2 || g->H[2] < 2) {
+    ocn_set_error(ctx, "%s: the closure reads two halo cells in x, y and z (the tapering factor at i + 1 reads the buoyancy at i + 2, the one at "
+                  "face Nz + 1 level Nz + 2); the grid has (%d, %d, %d)", fn, g->H[0], g->H[1], g->H[2]);
+    return OCN_EINVAL;
+  }
+  if ((h->rb.on && h->rb.loc == 1) || (h->rb.on && h->rb.disc == 1) || (h->cv.on && h->cv.disc == 1)) {
+    ocn_set_error(ctx, "%s: %s is on: next to this closure a CAVD / RBVD is vertically implicit with its coefficients at Face", fn,
+                  h->rb.on && h->rb.loc == 1 ? "a RiBasedVerticalDiffusivity at Center (its solve interpolates cell-centred coefficients, another "
+                                               "column type)" : "an explicit ConvectiveAdjustmentVerticalDiffusivity / RiBasedVerticalDiffusivity");
+    return OCN_EUNSUPPORTED;
+  }
+  ocn_hydro::Iso& s = h->iso;
+  hipStreamSynchronize(ctx->stream);
+  int rc;
+  if (!s.er33 && (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &s.er33))) return rc;
+  const size_t nb = s.er33->n * sizeof(double);
+  auto alloc = [&](double** p, size_t bytes) -> int {
+    if (*p) return OCN_OK;
+    if (hipMalloc((void**)p, bytes) != hipSuccess) {
+      ocn_set_error(ctx, "allocation of %zu bytes failed", bytes);
+      return OCN_ENOMEM;
+    }
+    return hipMemset(*p, 0, bytes) == hipSuccess ? OCN_OK : OCN_EHIP;
+  };
+  for (double*& p : s.w)
+    if ((rc = alloc(&p, nb))) return rc;
+  if ((rc = alloc(&s.t, (size_t)g->N[0] * g->N[1] * g->N[2] * sizeof(double)))) return rc;
+  // one coefficient array per distinct kappa_symmetric
+  std::vector<int> kzi((size_t)ntracers, 0);
+  std::vector<double> distinct;
+  for (int q = 0; q < ntracers; ++q) {
+    size_t e = 0;
+    while (e < distinct.size() && distinct[e] != kappa_symmetric[q]) ++e;
+    if (e == distinct.size()) distinct.push_back(kappa_symmetric[q]);
+    kzi[q] = (int)e;
+  }
+  while (s.kz.size() > distinct.size()) { hipFree(s.kz.back()); s.kz.pop_back(); }
+  while (s.kz.size() < distinct.size()) {
+    double* p = nullptr;
+    if ((rc = alloc(&p, nb))) return rc;
+    s.kz.push_back(p);
+  }
+  s.kzi = kzi;
+  s.ks.assign(kappa_symmetric, kappa_symmetric + ntracers);
+  s.kk.assign(kappa_skew, kappa_skew + ntracers);
+  s.p = HyIsoParam{max_slope * max_slope, minimum_bz};
+  // dz^f at face Nz + 2: the centres of the halo cells, whose faces continue with the top cell's width (grid_generation.jl:28-75)
+  s.dzf_top = g->h_dzf[g->N[2]];
+  if (!g->z_regular) {
+    const int n = g->N[2];
+    const std::vector<double>& F = g->nodeF[2];
+    const double d = F[n] - F[n - 1];
+    const double c1 = ((F[n] + d) + F[n]) / 2, c2 = ((F[n] + (d + d)) + (F[n] + d)) / 2;
+    s.dzf_top = c2 - c1;
+  }
+  s.on = true;
+  return OCN_OK;
+}
+
+ocn_hfield* ocn_hydro_isopycnal_field(ocn_hydro* h, int32_t which) {
+  if (!h || which != 0 || !h->iso.on) return nullptr;
+  return h->iso.er33;
 }
 
 /* ---- third slice: calculate_tendencies! and the whole time step ---------------------------------------------------------------- */
@@ -3406,6 +3635,7 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
   if (h->lg->H[0] < 1 || h->lg->H[1] < 1 || h->lg->H[2] < 1) return OCN_EINVAL;
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
+  hydro_iso_fluxes(h);
   hydro_flux_bcs(h);
   return api_done(h->lg->ctx, OCN_OK);
 }
@@ -3419,6 +3649,7 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
     for (ocn_hfield* f : h->gm) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
+  hydro_iso_fluxes(h);
   hydro_flux_bcs(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
 }

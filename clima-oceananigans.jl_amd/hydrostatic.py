@@ -628,12 +628,87 @@ class RiBasedVerticalDiffusivity:
                 f"kappa0={self.kappa0!r}, Ri0kappa={self.Ri0kappa!r}, Ridkappa={self.Ridkappa!r})")
 
 
+class FluxTapering:
+    """FluxTapering(max_slope): the slope limiter of an IsopycnalSkewSymmetricDiffusivity, eps = min(1, max_slope^2 / slope^2)
+    (isopycnal_skew_symmetric_diffusivity.jl:114-178)"""
+
+    def __init__(self, max_slope):
+        self.max_slope = float(max_slope)
+
+    def __repr__(self):
+        return f"FluxTapering({self.max_slope!r})"
+
+
+class SmallSlopeIsopycnalTensor:
+    """SmallSlopeIsopycnalTensor(minimum_bz = 0): d_z b is clipped from below at minimum_bz before every slope is formed
+    (isopycnal_rotation_tensor_components.jl:60-64)"""
+
+    def __init__(self, minimum_bz=0.0):
+        self.minimum_bz = float(minimum_bz)
+
+    def __repr__(self):
+        return f"SmallSlopeIsopycnalTensor(minimum_bz={self.minimum_bz!r})"
+
+
+class IsopycnalSkewSymmetricDiffusivity:
+    """IsopycnalSkewSymmetricDiffusivity(time_discretization; kappa_skew, kappa_symmetric, slope_limiter, isopycnal_tensor)
+    (TurbulenceClosures/turbulence_closure_implementations/isopycnal_skew_symmetric_diffusivity.jl): Gent-McWilliams (kappa_skew) plus
+    Redi (kappa_symmetric) on the tracers, each a number or {tracer: number}; slopes from the model's buoyancy, tapered by
+    slope_limiter; the kappa_symmetric R33 part is taken by the vertically implicit solve.  update_state recomputes the slopes and
+    diffusivity_fields["eps_R33"].  ValueError for what the library does not carry: the explicit discretization (the reference's own
+    cannot run), function, array or field coefficients, negative or non-finite numbers, another slope limiter or tensor"""
+
+    DISCRETIZATIONS = ("VerticallyImplicit", "Explicit")
+
+    def __init__(self, kappa_skew=0.0, kappa_symmetric=0.0, slope_limiter=None, isopycnal_tensor=None, time_discretization="VerticallyImplicit"):
+        name = type(self).__name__
+        if time_discretization not in self.DISCRETIZATIONS:
+            raise ValueError(f"time_discretization must be one of {self.DISCRETIZATIONS}, got {time_discretization!r}")
+        if time_discretization == "Explicit":
+            raise ValueError(f"{name}: ExplicitTimeDiscretization cannot run in the reference (explicit_kappa_dz_c's explicit method takes 9 "
+                             "arguments and is called with 10): only VerticallyImplicit exists")
+        slope_limiter = FluxTapering(1e-2) if slope_limiter is None else slope_limiter
+        isopycnal_tensor = SmallSlopeIsopycnalTensor() if isopycnal_tensor is None else isopycnal_tensor
+        if not isinstance(slope_limiter, FluxTapering):
+            raise ValueError(f"{name}(slope_limiter={slope_limiter!r}): FluxTapering(max_slope) is the slope limiter carried")
+        if not isinstance(isopycnal_tensor, SmallSlopeIsopycnalTensor):
+            raise ValueError(f"{name}(isopycnal_tensor={isopycnal_tensor!r}): only SmallSlopeIsopycnalTensor is supported, as in the reference")
+        if not (np.isfinite(slope_limiter.max_slope) and slope_limiter.max_slope >= 0):
+            raise ValueError(f"{name}: max_slope must be finite and >= 0, got {slope_limiter.max_slope!r}")
+        if not (np.isfinite(isopycnal_tensor.minimum_bz) and isopycnal_tensor.minimum_bz >= 0):
+            raise ValueError(f"{name}: minimum_bz must be finite and >= 0, got {isopycnal_tensor.minimum_bz!r}")
+        self.time_discretization = time_discretization
+        self.slope_limiter, self.isopycnal_tensor = slope_limiter, isopycnal_tensor
+        self.kappa_skew = self._coefficient(kappa_skew, "kappa_skew")
+        self.kappa_symmetric = self._coefficient(kappa_symmetric, "kappa_symmetric")
+
+    def _coefficient(self, value, what):
+        if isinstance(value, dict):
+            return {n: self._coefficient(v, f"{what}[{n!r}]") for n, v in value.items()}
+        if not _is_number(value):
+            kind = "function" if callable(value) and not hasattr(value, "__array__") else "array or field"
+            raise ValueError(f"{type(self).__name__}({what}={kind}): numbers (or {{tracer: number}}) only: function, array and field "
+                             "coefficients are not carried")
+        if not (np.isfinite(value) and value >= 0):
+            raise ValueError(f"{type(self).__name__}({what}={value!r}): must be finite and >= 0")
+        return float(value)
+
+    def coefficients(self, names):
+        """(kappa_skew, kappa_symmetric) of each tracer in names"""
+        of = lambda k, n: k.get(n, 0.0) if isinstance(k, dict) else k                    # noqa: E731
+        return (np.array([of(self.kappa_skew, n) for n in names] or [0.0]), np.array([of(self.kappa_symmetric, n) for n in names] or [0.0]))
+
+    def __repr__(self):
+        return (f"IsopycnalSkewSymmetricDiffusivity{{{self.time_discretization}TimeDiscretization}}(kappa_skew={self.kappa_skew!r}, "
+                f"kappa_symmetric={self.kappa_symmetric!r}, slope_limiter={self.slope_limiter!r}, isopycnal_tensor={self.isopycnal_tensor!r})")
+
+
 _CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
                   ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, HorizontalDivergenceScalarDiffusivity,
-                  HorizontalDivergenceScalarBiharmonicDiffusivity)
+                  HorizontalDivergenceScalarBiharmonicDiffusivity, IsopycnalSkewSymmetricDiffusivity)
 _KIND_CODE = {VerticalScalarDiffusivity: 0, HorizontalScalarDiffusivity: 1, HorizontalScalarBiharmonicDiffusivity: 2,
               ConvectiveAdjustmentVerticalDiffusivity: 3, RiBasedVerticalDiffusivity: 4, HorizontalDivergenceScalarDiffusivity: 5,
-              HorizontalDivergenceScalarBiharmonicDiffusivity: 6}      # OCN_CLOSURE_*
+              HorizontalDivergenceScalarBiharmonicDiffusivity: 6, IsopycnalSkewSymmetricDiffusivity: 7}      # OCN_CLOSURE_*
 # the closures of each order of the three-slot sum (Laplacian-order term, biharmonic-order term): the Horizontal one, the Divergence one
 _ORDERS = ((HorizontalScalarDiffusivity, HorizontalDivergenceScalarDiffusivity),
            (HorizontalScalarBiharmonicDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity))
@@ -895,7 +970,7 @@ class HydrostaticState:
 
     def set_closure(self, closure):
         """None | (nu, kappa | {tracer: kappa}) -- VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(); nu, kappa) -- | one
-        closure object | a tuple of them (at most one of each kind): HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
+        closure object | a tuple of them (at most one of each kind): IsopycnalSkewSymmetricDiffusivity, HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity,
         HorizontalDivergenceScalarDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
         ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity (at most one of the last two; at most one non-zero nu among
         the two closures of the Laplacian order and among the two of the biharmonic order); explicit terms summed in tuple order.
@@ -904,6 +979,9 @@ class HydrostaticState:
         names = list(self.tracers)
         PD = C.POINTER(C.c_double)
         zero = _ScalarClosure()
+        iso = parts.get(IsopycnalSkewSymmetricDiffusivity)
+        if iso is not None:
+            self._check_isopycnal(iso, parts)
 
         def coeffs(kind):
             c = parts.get(kind, zero)
@@ -934,8 +1012,20 @@ class HydrostaticState:
         nu, k = coeffs(VerticalScalarDiffusivity)
         check(self.lib.ocn_hydro_set_closure(self.h, nu, len(names), k.ctypes.data_as(PD)), self.grid.ctx.h)
         def kinds_of(kind):
-            kinds = [_KIND_CODE[k] for k in parts] if kind in parts else []
+            # the isopycnal closure's term is a pass of its own: the other setters take the tuple without it
+            kinds = [_KIND_CODE[k] for k in parts if k is kind or k is not IsopycnalSkewSymmetricDiffusivity] if kind in parts else []
             return len(kinds), (C.c_int32 * max(1, len(kinds)))(*kinds)
+
+        def set_iso():
+            c = iso or IsopycnalSkewSymmetricDiffusivity()
+            kk, ks = c.coefficients(names)
+            check(self.lib.ocn_hydro_set_isopycnal_diffusivity(self.h, c.DISCRETIZATIONS.index(c.time_discretization), c.slope_limiter.max_slope,
+                                                               c.isopycnal_tensor.minimum_bz, len(names), kk.ctypes.data_as(PD),
+                                                               ks.ctypes.data_as(PD), *kinds_of(IsopycnalSkewSymmetricDiffusivity)),
+                  self.grid.ctx.h)
+        # switched off first, so that a CAVD / RBVD form it refuses next to it (explicit, Center) can come on; switched on last
+        if iso is None:
+            set_iso()
 
         def set_cavd():
             cv = parts.get(ConvectiveAdjustmentVerticalDiffusivity, ConvectiveAdjustmentVerticalDiffusivity())
@@ -954,23 +1044,53 @@ class HydrostaticState:
         # at most one of the two is on: the one switched off goes first
         for setter in ((set_cavd, set_rbvd) if RiBasedVerticalDiffusivity in parts else (set_rbvd, set_cavd)):
             setter()
+        if iso is not None:
+            set_iso()
         self.closure = closure
+
+    def _check_isopycnal(self, iso, parts):
+        """the refusals of an IsopycnalSkewSymmetricDiffusivity in this model, before anything is set (ValueError, each with its reason)"""
+        name, g = "IsopycnalSkewSymmetricDiffusivity", self.grid
+        if self.buoyancy is None:
+            raise ValueError(f"{name}: the model has buoyancy=None: every slope would be 0 / 0")
+        if min(g.Hx, g.Hy) < 2:
+            raise ValueError(f"{name}: needs 2 halo cells in x and y (the flux at i + 1 reads the tapering factor at i + 1, which reads the "
+                             f"buoyancy at i + 2); the grid has ({g.Hx}, {g.Hy})")
+        if g.Hz < 2:
+            raise ValueError(f"{name}: needs 2 halo cells in z (the tapering factor at face Nz + 1 reads level Nz + 2); the grid has {g.Hz}")
+        unknown = [n for k in (iso.kappa_skew, iso.kappa_symmetric) if isinstance(k, dict) for n in k if n not in self.tracers]
+        if unknown:
+            raise ValueError(f"{name}: coefficients for {unknown}: the model's tracers are {list(self.tracers)}")
+        rb, cv = parts.get(RiBasedVerticalDiffusivity), parts.get(ConvectiveAdjustmentVerticalDiffusivity)
+        if rb is not None and rb.coefficient_z_location == "Center":
+            raise ValueError(f"{name} with a RiBasedVerticalDiffusivity at Center: its solve interpolates cell-centred coefficients, a different "
+                             "column type; use coefficient_z_location='Face'")
+        for c in (rb, cv):
+            if c is not None and c.time_discretization == "Explicit":
+                raise ValueError(f"{name} with an explicit {type(c).__name__}: next to this closure the vertical closures are vertically implicit")
 
     @property
     def diffusivity_fields(self):
         """{"kappa": HField, "nu": HField} of the ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity switched on
-        last ((Center, Center, Face), or (Center, Center, Center) for a RiBasedVerticalDiffusivity at Center; set by update_state), or
-        None before one was first switched on"""
+        last ((Center, Center, Face), or (Center, Center, Center) for a RiBasedVerticalDiffusivity at Center; set by update_state), plus
+        "eps_R33" (Center, Center, Face) while an IsopycnalSkewSymmetricDiffusivity is on; None before any of them was first switched
+        on"""
         hk, hn = self.lib.ocn_hydro_diffusivity_field(self.h, 0), self.lib.ocn_hydro_diffusivity_field(self.h, 1)
-        if not hk:
+        he = self.lib.ocn_hydro_isopycnal_field(self.h, 0)
+        if not hk and not he:
             return None
+        handles = {"kappa": hk, "nu": hn, "eps_R33": he}
         cached = getattr(self, "_diffusivity_fields", None)
-        if cached is None or cached["kappa"].h.value != hk or cached["nu"].h.value != hn:
-            total, interior, halo = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)()
-            check(self.lib.ocn_hfield_shape(C.c_void_p(hk), total, interior, halo), self.grid.ctx.h)
-            lz = Face if interior[2] == self.grid.Nz + 1 else Center
-            self._diffusivity_fields = {"kappa": HField(self.grid, (Center, Center, lz), handle=hk),
-                                        "nu": HField(self.grid, (Center, Center, lz), handle=hn)}
+        if cached is None or {n: (cached[n].h.value if n in cached else None) for n in handles} != handles:
+            fields = {}
+            if hk:
+                total, interior, halo = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)()
+                check(self.lib.ocn_hfield_shape(C.c_void_p(hk), total, interior, halo), self.grid.ctx.h)
+                lz = Face if interior[2] == self.grid.Nz + 1 else Center
+                fields = {"kappa": HField(self.grid, (Center, Center, lz), handle=hk), "nu": HField(self.grid, (Center, Center, lz), handle=hn)}
+            if he:
+                fields["eps_R33"] = HField(self.grid, (Center, Center, Face), handle=he)
+            self._diffusivity_fields = fields
         return self._diffusivity_fields
 
     def set_physics(self, momentum_advection, coriolis, tracer_advection):

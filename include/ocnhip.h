@@ -509,6 +509,29 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
  * leave them; Face: face Nz + 1 and the z halos zero; Center: the first z halo on either side a copy of the level next to it); NULL
  * before either closure was first switched on */
 ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which);
+/* closure = IsopycnalSkewSymmetricDiffusivity(discretization; kappa_skew, kappa_symmetric, slope_limiter = FluxTapering(max_slope),
+ * isopycnal_tensor = SmallSlopeIsopycnalTensor(minimum_bz)) (TurbulenceClosures/turbulence_closure_implementations/
+ * isopycnal_skew_symmetric_diffusivity.jl, isopycnal_rotation_tensor_components.jl): Gent-McWilliams plus Redi, on the tracers only.
+ * kappa_skew[q] and kappa_symmetric[q] are the numbers of tracer q.  update_state! stores the tapering factor, the slopes and
+ * eps_R33; calculate_tendencies! subtracts the divergence of the skew and symmetric fluxes from G^n of every tracer in a pass of its
+ * own (after the horizontal closures' pass: next to other explicit closures the sum differs from the reference's tuple sum by
+ * round-off); ab2_step! solves (1 - dt d_z K d_z) c = c* per column with K = kappa_symmetric eps_R33 plus the kappa of an implicit
+ * ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity (Face) that is on, together with the constant of
+ * ocn_hydro_set_closure.  NaN and +-Inf arise and propagate as in the reference (its min / max, its 0 / 0 at face 1 and face Nz + 1 of
+ * a horizontally uniform state).  `tuple` lists the kinds of the closure tuple (kind 7 exactly once; ntuple 0: this closure alone); the
+ * setters of the other closures take their tuple without kind 7.  All-zero kappas switch the closure off and free its fields.
+ * discretization 0 only (vertically implicit, the default).  OCN_EUNSUPPORTED, with the reason in ocn_last_error, for discretization 1
+ * (the reference's explicit method takes 9 arguments and is called with 10: it cannot run), a model without buoyancy (every slope
+ * would be 0 / 0), a RiBasedVerticalDiffusivity at Center or an explicit CAVD / RBVD that is on (their setters refuse the converse).
+ * OCN_EINVAL for any other discretization, a negative or non-finite kappa, max_slope or minimum_bz, an ntracers that is not the
+ * model's, fewer than 2 halo cells in x, y or z (eps at i + 1 reads b at i + 2; eps at face Nz + 1 reads level Nz + 2), a tuple with an
+ * unknown kind, with kind 7 twice (at most one such closure) or without it. */
+enum { OCN_CLOSURE_ISOPYCNAL_SKEW_SYMMETRIC = 7 };
+int ocn_hydro_set_isopycnal_diffusivity(ocn_hydro* h, int32_t discretization, double max_slope, double minimum_bz, int32_t ntracers,
+                                        const double* kappa_skew, const double* kappa_symmetric, int32_t ntuple, const int32_t* tuple);
+/* diffusivity_fields of the isopycnal closure: which 0 eps_R33, the tapered 33 component of the rotation tensor, a (Center, Center,
+ * Face) field owned by the handle (faces 1..Nz of the grid's columns, x / y halos filled, nothing in z); NULL while the closure is off */
+ocn_hfield* ocn_hydro_isopycnal_field(ocn_hydro* h, int32_t which);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
 int ocn_hydro_calculate_tendencies(ocn_hydro* h);
