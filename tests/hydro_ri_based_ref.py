@@ -90,7 +90,7 @@ class _Field3:
 
 def diffusivities(st):
     """{"kappa", "nu"}: parent arrays at (Center, Center, LZ) after calculate_diffusivities! and fill_halo_regions!"""
-    g, rb = st.grid, st.rbvd
+    g, rb = st.grid, getattr(st, "rbvd", None)          # a state whose closure hydro_convective_adjustment_ref.set_closure stored has none
     if rb is None:
         return _ca_diffusivities(st)
     Ri = richardson(st)

@@ -1,7 +1,9 @@
 """Seeded random configurations of the hydrostatic time step -- grid kind, sizes, halos, stretched / regular z, wall-bounded or periodic
 x, buoyancy, Coriolis, advection schemes, number of ranks (latitude bands, replicated or banded free surface) -- through the library
 (host emulation; `-m gpu`: libocnhip.so on one rank) against the single-domain oracle: owned rows bit for bit with the default tracer
-scheme (to 2e-11 with the higher-order ones, whose kernels share the Nonhydrostatic reconstructions)."""
+scheme (to 2e-11 with the higher-order ones, whose kernels share the Nonhydrostatic reconstructions).
+The closures, boundary conditions, flux-form / stretched schemes and implicit free surfaces added since are drawn, in combination, by
+tests/test_hydrostatic_random_features.py; this `draw` stays as it is and pins the older option space bit for bit."""
 import numpy as np
 import pytest
 

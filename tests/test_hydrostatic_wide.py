@@ -15,6 +15,7 @@ The helpers, references and tolerances are those of the small-grid modules (impo
 bit for bit and the schemes are second order, 1e-12 otherwise, 2e-11 of a field's largest value with the higher-order schemes.  Every case
 runs on the host emulation and, under `-m gpu`, on the GPU; the emulation takes the one-launch form of the sub-cycle, so k_se_multi,
 readfirstlane row indices and the 128 KB transforms are pinned by the GPU variants.
+`draw_wide` keeps the older option space; the features added since meet, on wide grids too, in tests/test_hydrostatic_random_features.py.
 """
 import zlib
 
