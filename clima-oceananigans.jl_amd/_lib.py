@@ -184,6 +184,8 @@ def load():
         "ocn_hydro_diffusivity_field": (P, [P, I]),
         "ocn_hydro_set_isopycnal_diffusivity": (I, [P, I, D, D, I, C.POINTER(D), C.POINTER(D), I, C.POINTER(C.c_int32)]),
         "ocn_hydro_isopycnal_field": (P, [P, I]),
+        "ocn_hydro_set_catke": (I, [P, I, I, D, PD, I, PD, C.c_int64, I, C.POINTER(C.c_int32)]),
+        "ocn_hydro_catke_field": (P, [P, I]),
         "ocn_hydro_calculate_tendencies": (I, [P]),
         "ocn_hydro_time_step": (I, [P, D, I]),
         "ocn_ifs_create": (I, [P, D, D, D, C.c_int64, C.POINTER(P)]),

@@ -1082,6 +1082,8 @@ __global__ void __launch_bounds__(256) k_hy_Gc_hi(HyMetric g, const double* __re
 
 // RiBasedVerticalDiffusivity: k_hy_ri_diff (its solve and explicit terms: hyconvect.h / hyclosure.h with the Center-location variants)
 #include "hyribased.h"
+// CATKEVerticalDiffusivity: k_hy_catke_diff, the TKE source terms k_hy_catke_src and the solve with an implicit linear term
+#include "hycatke.h"
 // IsopycnalSkewSymmetricDiffusivity: the slope pass of update_state!, the flux pass of calculate_tendencies!, the solve's coefficients
 #include "hyisopycnal.h"
 
@@ -1330,7 +1332,19 @@ struct ocn_hydro {
     int loc = 0, taper = 0;
     bool nzu = false, nzc = false;
     HyRiParam rp{};
-  } cv, rb;
+  } cv, rb, ck;
+  // CATKEVerticalDiffusivity (hycatke.h), vertically implicit: ck is its Cavd (kap = K^c, nu = K^u, coefficients at Face); K^e and L^e
+  // of the tracer e (index eidx of c), the wall distance of faces 1..Nz + 1 and the static surface buoyancy flux Q^b (Nx Ny, null: zero)
+  // on the device; lin: L^e enters the diagonal of e's solve (the closure stands alone: a tuple's diagonal has no linear term in the
+  // reference)
+  struct Catke {
+    ocn_hfield *Ke = nullptr, *Le = nullptr;
+    HyCatkeParam p{};
+    int eidx = -1;
+    bool lin = false;
+    double *dw = nullptr, *Qb = nullptr;
+    bool has_qb = false;
+  } catke;
   int vk_last = 0;                           // the closure (OCN_CLOSURE_*) whose fields ocn_hydro_diffusivity_field returns
   // IsopycnalSkewSymmetricDiffusivity (hyisopycnal.h), vertically implicit: per-tracer kappa_symmetric / kappa_skew, the stored fields
   // (eps_R33 a field of the handle, eps, R13, R23, R31, R32 plain arrays of its parent shape), the coefficient arrays of the tracers'
@@ -1518,7 +1532,7 @@ static void hydro_rb_diffusivities(ocn_hydro* h) {
   hfield_fill(N, h->rb.loc == 1);
 }
 // the variable-coefficient vertical closure that is on (CAVD or RBVD, never both), or null
-static const ocn_hydro::Cavd* hydro_vk(const ocn_hydro* h) { return h->cv.on ? &h->cv : h->rb.on ? &h->rb : nullptr; }
+static const ocn_hydro::Cavd* hydro_vk(const ocn_hydro* h) { return h->cv.on ? &h->cv : h->rb.on ? &h->rb : h->ck.on ? &h->ck : nullptr; }
 // the closure's implicit solve for u (nu), v (nu) or tracers (kappa): on when it is vertically implicit with a non-zero coefficient;
 // an IsopycnalSkewSymmetricDiffusivity always solves the tracers (and never u or v: its viscosity is zero)
 static bool hydro_cv_implicit_uv(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hydro_vk(h); return v && v->disc == 0 && v->nzu; }
@@ -1554,8 +1568,42 @@ static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of
     return HyCvSolve{h->iso.kz[h->iso.kzi[q - 1]], (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->iso.t};
   }
   const ocn_hydro::Cavd* v = hydro_vk(h);
-  const ocn_hfield* K = q == 0 ? v->nu : v->kap;
+  const ocn_hfield* K = q == 0 ? v->nu : (h->ck.on && q - 1 == h->catke.eidx) ? h->catke.Ke : v->kap;
   return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, v->t};
+}
+// the tracer e of a CATKEVerticalDiffusivity that stands alone: its solve carries L^e on the diagonal (q: entry of h->kap)
+static bool hydro_catke_lin(const ocn_hydro* h, int q) { return h->ck.on && h->catke.lin && q - 1 == h->catke.eidx; }
+static HyCvLin hydro_catke_lin_arg(const ocn_hydro* h) {
+  const ocn_hfield* L = h->catke.Le;
+  return HyCvLin{L->d, (long)L->T[0], (long)L->T[0] * L->T[1]};
+}
+// calculate_diffusivities! of the CATKEVerticalDiffusivity (hycatke.h): one launch over the interior columns, then the x / y fills of
+// K^u (with the band exchange), the field whose halos the solves and the w-shear term of u and v read
+static void hydro_catke_diffusivities(ocn_hydro* h) {
+  const ocn_hgrid* g = h->lg;
+  const ocn_hydro::Catke& k = h->catke;
+  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  const ocn_hfield *u = h->u, *v = h->v, *e = h->c[k.eidx];
+  dim3 b, gr;
+  hy_cols(g, b, gr);
+  ocn_launch(k_hy_catke_diff, gr, b, g->ctx->stream, hy_grid(g), h->buoy, k.p, (const double*)k.dw, k.has_qb ? (const double*)k.Qb : (const double*)nullptr,
+             (const double*)u->d, (const double*)v->d, T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr,
+             (const double*)e->d, Ku->d, Kc->d, k.Ke->d, k.Le->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],
+             (long)e->T[0], (long)e->T[0] * e->T[1], (long)Ku->T[0], (long)Ku->T[0] * Ku->T[1], (long)k.Le->T[0], (long)k.Le->T[0] * k.Le->T[1]);
+  hfield_fill(h->ck.nu, false);
+}
+// the source terms of the TKE tendency (shear production, buoyancy flux), after the tracer pass and before the flux conditions
+static void hydro_catke_sources(ocn_hydro* h) {
+  if (!h->ck.on) return;
+  const ocn_hgrid* g = h->lg;
+  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  const ocn_hfield *u = h->u, *v = h->v, *e = h->c[h->catke.eidx];
+  dim3 b, gr;
+  hy_cols(g, b, gr);
+  ocn_launch(k_hy_catke_src, gr, b, g->ctx->stream, hy_grid(g), h->buoy, (const double*)u->d, (const double*)v->d,
+             T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, (const double*)Ku->d,
+             (const double*)Kc->d, h->gn[2 + h->catke.eidx]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],
+             (long)e->T[0], (long)e->T[0] * e->T[1], (long)Ku->T[0], (long)Ku->T[0] * Ku->T[1]);
 }
 // loc: 0 a tracer, 1 u, 2 v (+ 3 for Center-location coefficients)
 static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q, double dt) {
@@ -1565,7 +1613,8 @@ static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q
   const HyCvSolve s = hydro_cv_solve(h, q);
   const long sy = f->T[0], sz = (long)f->T[0] * f->T[1];
   loc += hydro_cv_center(h) ? 3 : 0;
-  if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+  if (loc == 0 && hydro_catke_lin(h, q)) ocn_launch(k_hy_cv_implicit_lin, gr, b, g->ctx->stream, f->d, s, hydro_catke_lin_arg(h), hy_grid(g), dt, sy, sz);
+  else if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 1) ocn_launch(k_hy_cv_implicit<1>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 2) ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
   else if (loc == 3) ocn_launch(k_hy_cv_implicit<3>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
@@ -1581,6 +1630,7 @@ static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   hy_w_launch(h->u, h->v, h->w);
   if (h->cv.on) hydro_cv_diffusivities(h);
   if (h->rb.on) hydro_rb_diffusivities(h);
+  if (h->ck.on) hydro_catke_diffusivities(h);
   if (h->iso.on) hydro_iso_diffusivities(h);
   if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, h->bT >= 0 ? h->c[h->bT] : nullptr, h->bS >= 0 ? h->c[h->bS] : nullptr);
   hfield_fill(h->w);
@@ -2083,7 +2133,10 @@ static int hydro_fused_tracers(ocn_hydro* h, double dt, double chi, bool* pressu
         dim3 b2, g2;
         hy_cols(g, b2, g2);
         ocn_hfield* f = h->c[q];
-        if (hydro_cv_center(h))
+        if (hydro_catke_lin(h, 1 + (int)q))
+          ocn_launch(k_hy_cv_ab2_lin, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hydro_catke_lin_arg(h), hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+        else if (hydro_cv_center(h))
           ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
                      hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
         else
@@ -2820,7 +2873,11 @@ void ocn_hydro_destroy(ocn_hydro* h) {
   for (auto& e : h->cconst) hipFree(e.second);
   for (auto& f : h->fbc)
     for (auto& b : f) hipFree(b.d);
-  for (ocn_hydro::Cavd* v : {&h->cv, &h->rb}) {
+  if (h->catke.Ke) ocn_hfield_destroy(h->catke.Ke);
+  if (h->catke.Le) ocn_hfield_destroy(h->catke.Le);
+  hipFree(h->catke.dw);
+  hipFree(h->catke.Qb);
+  for (ocn_hydro::Cavd* v : {&h->cv, &h->rb, &h->ck}) {
     if (v->kap) ocn_hfield_destroy(v->kap);
     if (v->nu) ocn_hfield_destroy(v->nu);
     hipFree(v->t);
@@ -3170,7 +3227,7 @@ int ocn_hydro_set_flux_bc(ocn_hydro* h, int32_t field, int32_t side, int32_t kin
 // formulation is set for the order (ocn_hydro_set_horizontal_formulation, called before) and the Horizontal one otherwise; the
 // tracers' term is always the Horizontal one (a HorizontalDivergence closure has no tracer flux)
 static void hydro_tuple_order(const ocn_hydro* h, int ntuple, const int32_t* tuple, int order[3], int order_c[3]) {
-  bool has[7] = {false, false, false, false, false, false, false};
+  bool has[9] = {false, false, false, false, false, false, false, false, false};
   for (int q = 0; q < ntuple; ++q) has[tuple[q]] = true;
   for (int who = 0; who < 2; ++who) {
     int* o = who ? order_c : order;
@@ -3249,6 +3306,10 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
   if (on && h->iso.on && discretization == 1) {
     ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: an IsopycnalSkewSymmetricDiffusivity is on: next to it the closure is vertically "
                   "implicit (the explicit form is not carried in one tuple with it)");
+    return OCN_EUNSUPPORTED;
+  }
+  if (on && h->ck.on) {
+    ocn_set_error(ctx, "ocn_hydro_set_convective_adjustment: a CATKEVerticalDiffusivity is on (at most one variable-coefficient vertical closure)");
     return OCN_EUNSUPPORTED;
   }
   if (on && h->rb.on) {
@@ -3347,6 +3408,10 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
                   "carried in one tuple with it)", fn);
     return OCN_EUNSUPPORTED;
   }
+  if (on && h->ck.on) {
+    ocn_set_error(ctx, "%s: a CATKEVerticalDiffusivity is on (at most one variable-coefficient vertical closure)", fn);
+    return OCN_EUNSUPPORTED;
+  }
   if (on && h->cv.on) {
     ocn_set_error(ctx, "%s: a ConvectiveAdjustmentVerticalDiffusivity is on (at most one variable-coefficient vertical closure)", fn);
     return OCN_EINVAL;
@@ -3388,6 +3453,147 @@ ocn_hfield* ocn_hydro_diffusivity_field(ocn_hydro* h, int32_t which) {
   if (!h || which < 0 || which > 1) return nullptr;
   const ocn_hydro::Cavd& v = h->vk_last == OCN_CLOSURE_RI_BASED ? h->rb : h->cv;
   return which == 0 ? v.kap : v.nu;
+}
+
+/* closure = CATKEVerticalDiffusivity(VerticallyImplicitTimeDiscretization(); CD, mixing_length) (CATKEVerticalDiffusivities/), alone
+ * or in a tuple; hycatke.h */
+int ocn_hydro_set_catke(ocn_hydro* h, int32_t on, int32_t discretization, double CD, const double* mixing_length, int32_t e_index,
+                        const double* top_buoyancy_flux, int64_t n_flux, int32_t ntuple, const int32_t* tuple) {
+  if (!h) return OCN_EINVAL;
+  ocn_hgrid* g = h->lg;
+  ocn_ctx* ctx = g->ctx;
+  const char* fn = "ocn_hydro_set_catke";
+  if (!on) {
+    h->ck.on = false;
+    return OCN_OK;
+  }
+  if (discretization == 1) {
+    ocn_set_error(ctx, "%s: with ExplicitTimeDiscretization the reference's dissipation silently evaluates to zero through a fallback method "
+                  "(TKE would only grow); only the vertically implicit form (0) is carried", fn);
+    return OCN_EUNSUPPORTED;
+  }
+  if (discretization != 0) {
+    ocn_set_error(ctx, "%s: discretization 0 (vertically implicit), got %d", fn, (int)discretization);
+    return OCN_EINVAL;
+  }
+  if (e_index < 0 || e_index >= (int)h->c.size()) {
+    ocn_set_error(ctx, "%s: tracers must contain e to represent turbulent kinetic energy (e_index %d of %d tracers)", fn, (int)e_index, (int)h->c.size());
+    return OCN_EINVAL;
+  }
+  if (!mixing_length) {
+    ocn_set_error(ctx, "%s: the 25 mixing-length parameters are missing", fn);
+    return OCN_EINVAL;
+  }
+  // Cb, Cs, Cbu, Cbc, Cbe, Csu, Csc, Cse, Cdu, Cdc, Cde, CAu, CAc, CAe, CASu, CASc, CASe, CKu-, CKur, CKc-, CKcr, CKe-, CKer, CKRiw, CKRic
+  const double* m = mixing_length;
+  static const char* names[25] = {"Cb", "Cs", "Cbu", "Cbc", "Cbe", "Csu", "Csc", "Cse", "Cdu", "Cdc", "Cde", "CAu", "CAc", "CAe", "CASu", "CASc",
+                                  "CASe", "CKu-", "CKur", "CKc-", "CKcr", "CKe-", "CKer", "CKRiw", "CKRic"};
+  for (int q = 0; q < 25; ++q) {
+    // 0, 1: > 0, Inf legal (the inert value); 2..10, 17, 19, 21, 23: finite and > 0 (a zero meets an Inf length, or divides);
+    // 11..16, 18, 20, 22: finite and >= 0; 24: finite
+    const bool pos = q <= 10 || q == 17 || q == 19 || q == 21 || q == 23;
+    const bool ok = q < 2 ? m[q] > 0 : q == 24 ? std::isfinite(m[q]) : pos ? (m[q] > 0 && std::isfinite(m[q])) : (m[q] >= 0 && std::isfinite(m[q]));
+    if (!ok) {
+      ocn_set_error(ctx, "%s: mixing-length parameter %s = %g: %s (the reference would compute 0 * Inf, divide by it, or mix backwards)", fn, names[q],
+                    m[q], q < 2 ? "must be > 0 (Inf is the inert value)" : q == 24 ? "must be finite" : pos ? "must be finite and > 0" : "must be finite and >= 0");
+      return OCN_EINVAL;
+    }
+  }
+  if (!(CD >= 0) || !std::isfinite(CD)) {
+    ocn_set_error(ctx, "%s: CD must be finite and >= 0 (%g)", fn, CD);
+    return OCN_EINVAL;
+  }
+  if (n_flux != 0 && (!top_buoyancy_flux || n_flux != (int64_t)g->N[0] * g->N[1])) {
+    ocn_set_error(ctx, "%s: the top buoyancy flux holds Nx * Ny = %ld numbers (or none), got %ld", fn, (long)g->N[0] * g->N[1], (long)n_flux);
+    return OCN_EINVAL;
+  }
+  if (ntuple < 0 || (ntuple > 0 && !tuple)) {
+    ocn_set_error(ctx, "%s: a closure tuple of %d entries without its kinds", fn, (int)ntuple);
+    return OCN_EINVAL;
+  }
+  if (ntuple > 3) {
+    ocn_set_error(ctx, "%s: a tuple of %d closures: the reference has no shear_production method beyond three", fn, (int)ntuple);
+    return OCN_EUNSUPPORTED;
+  }
+  int nck = 0, seen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int q = 0; q < ntuple; ++q) {
+    const int kind = tuple[q];
+    if (kind < OCN_CLOSURE_VERTICAL_SCALAR || kind > OCN_CLOSURE_CATKE) {
+      ocn_set_error(ctx, "%s: unknown closure kind %d at tuple position %d", fn, kind, q);
+      return OCN_EINVAL;
+    }
+    if (seen[kind]++) {
+      ocn_set_error(ctx, "%s: %s", fn, kind == OCN_CLOSURE_CATKE ? "can't have two CATKEs in one closure tuple" : "a closure tuple holds at most one closure of each kind");
+      return OCN_EINVAL;
+    }
+    if (kind == OCN_CLOSURE_CONVECTIVE_ADJUSTMENT || kind == OCN_CLOSURE_RI_BASED || kind == OCN_CLOSURE_ISOPYCNAL_SKEW_SYMMETRIC) {
+      ocn_set_error(ctx, "%s: CATKEVerticalDiffusivity next to a ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or "
+                    "IsopycnalSkewSymmetricDiffusivity is out of scope (one set of column coefficients per model)", fn);
+      return OCN_EUNSUPPORTED;
+    }
+    nck += kind == OCN_CLOSURE_CATKE;
+  }
+  if (ntuple > 0 && nck == 0) {
+    ocn_set_error(ctx, "%s: the closure tuple holds no CATKEVerticalDiffusivity", fn);
+    return OCN_EINVAL;
+  }
+  if (h->cv.on || h->rb.on || h->iso.on) {
+    ocn_set_error(ctx, "%s: a ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity or IsopycnalSkewSymmetricDiffusivity is on", fn);
+    return OCN_EUNSUPPORTED;
+  }
+  if (g->H[0] < 1 || g->H[1] < 1 || g->H[2] < 1) {
+    ocn_set_error(ctx, "%s: the closure reads one halo cell in x, y and z (the grid has %d, %d, %d)", fn, g->H[0], g->H[1], g->H[2]);
+    return OCN_EINVAL;
+  }
+  int order[3], order_c[3];
+  hydro_tuple_order(h, ntuple, tuple, order, order_c);
+  ocn_hydro::Cavd& ck = h->ck;
+  ocn_hydro::Catke& k = h->catke;
+  OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  int rc;
+  if (!ck.kap) {
+    if ((rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &ck.kap)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &ck.nu)) ||
+        (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &k.Ke)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_CENTER, &k.Le)))
+      return rc;
+    const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
+    if (hipMalloc((void**)&ck.t, nt * sizeof(double)) != hipSuccess) {
+      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
+      return OCN_ENOMEM;
+    }
+    // the wall distance of faces 1..Nz + 1: min(depth, height above the bottom) (mixing_length.jl:97-102)
+    const int Nz = g->N[2], off = g->z_regular ? g->H[2] : 0;
+    std::vector<double> dw((size_t)Nz + 1);
+    const double top = g->nodeF[2][off + Nz], bot = g->nodeF[2][off];
+    for (int K = 1; K <= Nz + 1; ++K) {
+      const double z = g->nodeF[2][off + K - 1];
+      dw[K - 1] = std::fmin(top - z, z - bot);
+    }
+    if ((rc = upload(ctx, dw, &k.dw))) return rc;
+    if (hipMalloc((void**)&k.Qb, (size_t)g->N[0] * g->N[1] * sizeof(double)) != hipSuccess) {
+      ocn_set_error(ctx, "allocation of %zu bytes failed", (size_t)g->N[0] * g->N[1] * sizeof(double));
+      return OCN_ENOMEM;
+    }
+  }
+  k.has_qb = n_flux != 0;
+  if (k.has_qb) OCN_HIP_CHECK(ctx, hipMemcpy(k.Qb, top_buoyancy_flux, (size_t)n_flux * sizeof(double), hipMemcpyHostToDevice));
+  k.p = HyCatkeParam{CD, std::fmin(m[0], m[2]), std::fmin(m[0], m[3]), std::fmin(m[0], m[4]), std::fmin(m[1], m[5]), std::fmin(m[1], m[6]),
+                     std::fmin(m[1], m[7]), m[8], m[9], m[10], m[12], m[13], m[15], m[16], m[17], m[18], m[19], m[20], m[21], m[22], m[23], m[24]};
+  k.eidx = e_index;
+  k.lin = ntuple == 0;
+  ck.on = true;
+  ck.disc = 0;
+  ck.loc = 0;
+  ck.nzu = ck.nzc = true;
+  for (int e = 0; e < 3; ++e) { ck.order[e] = order[e]; ck.order_c[e] = order_c[e]; }
+  h->vk_last = OCN_CLOSURE_CATKE;
+  return OCN_OK;
+}
+
+/* the fields of the CATKEVerticalDiffusivity: which 0 K^u, 1 K^c, 2 K^e ((Center, Center, Face)), 3 L^e ((Center, Center, Center));
+ * NULL before the closure was first switched on */
+ocn_hfield* ocn_hydro_catke_field(ocn_hydro* h, int32_t which) {
+  if (!h || which < 0 || which > 3) return nullptr;
+  return which == 0 ? h->ck.nu : which == 1 ? h->ck.kap : which == 2 ? h->catke.Ke : h->catke.Le;
 }
 
 /* closure = IsopycnalSkewSymmetricDiffusivity(VerticallyImplicitTimeDiscretization(); kappa_skew, kappa_symmetric, slope_limiter =
@@ -3453,6 +3659,10 @@ int ocn_hydro_set_isopycnal_diffusivity(ocn_hydro* h, int32_t discretization, do
     hipStreamSynchronize(ctx->stream);
     hydro_iso_release(h);
     return OCN_OK;
+  }
+  if (h->ck.on) {
+    ocn_set_error(ctx, "%s: a CATKEVerticalDiffusivity is on: the two closures in one tuple are out of scope", fn);
+    return OCN_EUNSUPPORTED;
   }
   if (h->buoy.kind == 0 || h->bT < 0) {
     ocn_set_error(ctx, "%s: the model has no buoyancy: every slope would be 0 / 0", fn);
@@ -3636,6 +3846,7 @@ int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
   hydro_iso_fluxes(h);
+  hydro_catke_sources(h);
   hydro_flux_bcs(h);
   return api_done(h->lg->ctx, OCN_OK);
 }
@@ -3650,6 +3861,7 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
   hydro_iso_fluxes(h);
+  hydro_catke_sources(h);
   hydro_flux_bcs(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
 }

@@ -703,12 +703,113 @@ class IsopycnalSkewSymmetricDiffusivity:
                 f"kappa_symmetric={self.kappa_symmetric!r}, slope_limiter={self.slope_limiter!r}, isopycnal_tensor={self.isopycnal_tensor!r})")
 
 
+class _Parameters:
+    """a parameter struct of the reference (Base.@kwdef): PARAMETERS lists (name, the reference's name, default); the constructor takes
+    either spelling as a keyword (Python folds most of the reference's superscripts into the plain names: Cᵇu is Cbu)"""
+
+    PARAMETERS = ()
+
+    def __init__(self, **kw):
+        alias = {ref: name for name, ref, _ in self.PARAMETERS}
+        values = {name: default for name, _, default in self.PARAMETERS}
+        for key, value in kw.items():
+            name = alias.get(key, key)
+            if name not in values:
+                raise ValueError(f"{type(self).__name__}: unknown parameter {key!r}: {', '.join(values)}")
+            if not _is_number(value):
+                raise ValueError(f"{type(self).__name__}({key}={value!r}): a number")
+            values[name] = float(value)
+        for name, value in values.items():
+            setattr(self, name, value)
+
+    def values(self):
+        return [getattr(self, name) for name, _, _ in self.PARAMETERS]
+
+    def __repr__(self):
+        return f"{type(self).__name__}(" + ", ".join(f"{name}={getattr(self, name)!r}" for name, _, _ in self.PARAMETERS) + ")"
+
+
+class MixingLength(_Parameters):
+    """MixingLength{FT} of CATKEVerticalDiffusivity (CATKEVerticalDiffusivities/mixing_length.jl:65-91), the reference's 25 parameters and
+    defaults, in its order (the order of ocn_hydro_set_catke's array)"""
+
+    PARAMETERS = (("Cb", "Cᵇ", float("inf")), ("Cs", "Cˢ", float("inf")), ("Cbu", "Cᵇu", 1.55), ("Cbc", "Cᵇc", 0.01), ("Cbe", "Cᵇe", 0.60),
+                  ("Csu", "Cˢu", 5.1), ("Csc", "Cˢc", 4.3), ("Cse", "Cˢe", 1.49), ("Cdu", "Cᵟu", 0.5), ("Cdc", "Cᵟc", 0.5), ("Cde", "Cᵟe", 0.5),
+                  ("CAu", "Cᴬu", 0.0), ("CAc", "Cᴬc", 0.0), ("CAe", "Cᴬe", 0.0), ("CAsu", "Cᴬˢu", 0.0), ("CAsc", "Cᴬˢc", 0.0), ("CAse", "Cᴬˢe", 0.0),
+                  ("CKum", "Cᴷu⁻", 0.14), ("CKur", "Cᴷuʳ", 0.1), ("CKcm", "Cᴷc⁻", 0.35), ("CKcr", "Cᴷcʳ", 0.05), ("CKem", "Cᴷe⁻", 0.49),
+                  ("CKer", "Cᴷeʳ", 17.0), ("CKRiw", "CᴷRiʷ", 30.0), ("CKRic", "CᴷRiᶜ", 1.1))
+
+
+class SurfaceTKEFlux(_Parameters):
+    """SurfaceTKEFlux{FT} (CATKEVerticalDiffusivities/surface_TKE_flux.jl:25-28): Qe = -CD (CWu_star u*^3 + CWw_delta w_delta^3)"""
+
+    PARAMETERS = (("CWu_star", "Cᵂu★", 0.01), ("CWw_delta", "CᵂwΔ", 40.0))
+
+
+class CATKEVerticalDiffusivity:
+    """CATKEVerticalDiffusivity(time_discretization; CD, mixing_length, surface_TKE_flux) (TurbulenceClosures/
+    turbulence_closure_implementations/CATKEVerticalDiffusivities/): vertical mixing from the prognostic turbulent kinetic energy, the
+    tracer "e".  update_state computes Ku, Kc, Ke (Center, Center, Face) and Le; u and v are solved with Ku, the tracers with Kc, e with
+    Ke and, where the closure stands alone, Le on the diagonal; e's tendency gets shear production and buoyancy flux, its top flux is
+    the reference's top_tke_flux (it overrides a condition given for e's top).  Only "VerticallyImplicit" runs: with "Explicit" the
+    reference's dissipation silently evaluates to zero through a fallback method"""
+
+    DISCRETIZATIONS = ("VerticallyImplicit", "Explicit")
+
+    def __init__(self, time_discretization="VerticallyImplicit", CD=0.81, mixing_length=None, surface_TKE_flux=None, **kw):
+        if time_discretization not in self.DISCRETIZATIONS:
+            raise ValueError(f"time_discretization must be one of {self.DISCRETIZATIONS}, got {time_discretization!r}")
+        if "Cᴰ" in kw:
+            CD = kw.pop("Cᴰ")
+        if kw:
+            raise ValueError(f"CATKEVerticalDiffusivity: unknown arguments {sorted(kw)}")
+        self.time_discretization = time_discretization
+        self.CD = float(CD)
+        self.mixing_length = MixingLength() if mixing_length is None else mixing_length
+        self.surface_TKE_flux = SurfaceTKEFlux() if surface_TKE_flux is None else surface_TKE_flux
+        if not isinstance(self.mixing_length, MixingLength) or not isinstance(self.surface_TKE_flux, SurfaceTKEFlux):
+            raise ValueError("CATKEVerticalDiffusivity: mixing_length is a MixingLength, surface_TKE_flux a SurfaceTKEFlux")
+
+    def check(self):
+        """ValueError for a parameter with which the reference would compute 0 * Inf, divide by zero or mix backwards"""
+        name = "CATKEVerticalDiffusivity"
+        if self.time_discretization == "Explicit":
+            raise ValueError(f"{name}: with ExplicitTimeDiscretization the reference's dissipation silently evaluates to zero through a "
+                             "fallback method (dissipation has no method for the arguments the tendency passes): only VerticallyImplicit runs")
+        if not (np.isfinite(self.CD) and self.CD >= 0):
+            raise ValueError(f"{name}: CD must be finite and >= 0, got {self.CD!r}")
+        m = self.mixing_length
+        for n, _, _ in m.PARAMETERS:
+            v = getattr(m, n)
+            if n in ("Cb", "Cs"):
+                ok, want = v > 0, "> 0 (Inf is the inert value)"
+            elif n == "CKRic":
+                ok, want = np.isfinite(v), "finite"
+            elif n[:2] in ("Cb", "Cs", "Cd") or n in ("CKum", "CKcm", "CKem", "CKRiw"):
+                ok, want = np.isfinite(v) and v > 0, "finite and > 0"
+            else:
+                ok, want = np.isfinite(v) and v >= 0, "finite and >= 0"
+            if not ok:
+                raise ValueError(f"{name}: mixing-length parameter {n} = {v!r} must be {want}: the reference would compute 0 * Inf, divide "
+                                 "by zero or mix backwards")
+        s = self.surface_TKE_flux
+        for n, _, _ in s.PARAMETERS:
+            v = getattr(s, n)
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{name}: surface TKE flux parameter {n} = {v!r} must be finite and >= 0")
+
+    def __repr__(self):
+        return (f"CATKEVerticalDiffusivity{{{self.time_discretization}TimeDiscretization}}(CD={self.CD!r}, "
+                f"mixing_length={self.mixing_length!r}, surface_TKE_flux={self.surface_TKE_flux!r})")
+
+
 _CLOSURE_KINDS = (HorizontalScalarDiffusivity, HorizontalScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
                   ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, HorizontalDivergenceScalarDiffusivity,
-                  HorizontalDivergenceScalarBiharmonicDiffusivity, IsopycnalSkewSymmetricDiffusivity)
+                  HorizontalDivergenceScalarBiharmonicDiffusivity, IsopycnalSkewSymmetricDiffusivity, CATKEVerticalDiffusivity)
 _KIND_CODE = {VerticalScalarDiffusivity: 0, HorizontalScalarDiffusivity: 1, HorizontalScalarBiharmonicDiffusivity: 2,
               ConvectiveAdjustmentVerticalDiffusivity: 3, RiBasedVerticalDiffusivity: 4, HorizontalDivergenceScalarDiffusivity: 5,
-              HorizontalDivergenceScalarBiharmonicDiffusivity: 6, IsopycnalSkewSymmetricDiffusivity: 7}      # OCN_CLOSURE_*
+              HorizontalDivergenceScalarBiharmonicDiffusivity: 6, IsopycnalSkewSymmetricDiffusivity: 7,
+              CATKEVerticalDiffusivity: 8}      # OCN_CLOSURE_*
 # the closures of each order of the three-slot sum (Laplacian-order term, biharmonic-order term): the Horizontal one, the Divergence one
 _ORDERS = ((HorizontalScalarDiffusivity, HorizontalDivergenceScalarDiffusivity),
            (HorizontalScalarBiharmonicDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity))
@@ -733,6 +834,8 @@ def closure_parts(closure):
         if kind not in _CLOSURE_KINDS:
             raise ValueError(f"unsupported closure {c!r}: {', '.join(k.__name__ for k in _CLOSURE_KINDS)}")
         if kind in parts:
+            if kind is CATKEVerticalDiffusivity:
+                raise ValueError("Can't have two CATKEs in one closure tuple.")
             raise ValueError(f"a closure tuple holds at most one {kind.__name__}")
         parts[kind] = c
     # one term of each order per field: the explicit terms are a three-slot sum (Laplacian order, biharmonic order, vertical)
@@ -928,11 +1031,77 @@ class HydrostaticState:
             if bad:
                 raise ValueError(f"unknown sides {bad} of {n}: {SIDES}")
         plan = [(f, s, *self._flux_args(n, side, bcs.get(n, {}).get(side))) for f, n in enumerate(names) for s, side in enumerate(SIDES)]
+        catke = closure_parts(getattr(self, "closure", None)).get(CATKEVerticalDiffusivity)
+        Qb = None
+        if catke is not None:
+            Qb, Qe = self._catke_fluxes(catke, bcs)
+            at = names.index("e") * len(SIDES) + SIDES.index("top")
+            if np.ndim(Qe) == 0:          # a zero flux is no condition: nothing is launched for it
+                plan[at] = plan[at][:2] + ((1, float(Qe), None) if Qe != 0 else (0, 0.0, None))
+            else:
+                plan[at] = plan[at][:2] + (2, 0.0, np.ascontiguousarray(Qe.ravel(order="F")))
         PD = C.POINTER(C.c_double)
         for f, s, kind, value, arr in plan:
             check(self.lib.ocn_hydro_set_flux_bc(self.h, f, s, kind, value, None if arr is None else arr.ctypes.data_as(PD),
                                                  0 if arr is None else arr.size), self.grid.ctx.h)
         self.boundary_conditions = bcs
+        if catke is not None:
+            self._send_catke(catke, Qb)
+
+    def _catke_fluxes(self, catke, bcs):
+        """(Qb, Qe) of a CATKEVerticalDiffusivity from the top conditions `bcs` holds: the static surface buoyancy flux of the convective
+        mixing length (top_buoyancy_flux: g (alpha Q_T - beta Q_S), or the buoyancy tracer's condition; 0 without buoyancy) and the top
+        flux of e (top_tke_flux, surface_TKE_flux.jl:50-77, with Qu and Qv taken at (i, j)); numbers, or (Nx, Ny) arrays"""
+        g = self.grid
+
+        def top(name):
+            bc = bcs.get(name, {}).get("top")
+            if isinstance(bc, LinearDrag):
+                raise ValueError(f"{bc!r} on the top of {name} next to a CATKEVerticalDiffusivity: the top flux of e and the convective mixing "
+                                 "length are built once from the top conditions of u, v and the buoyancy's tracers, and a linear drag makes that "
+                                 "flux depend on the state")
+            kind, value, arr = self._flux_args(name, "top", bc)
+            return value if kind != 2 else arr.reshape((g.Nx, g.Ny), order="F")
+        Qu, Qv = top("u"), top("v")
+        b = self.buoyancy
+        if b is None:
+            Qb = 0.0
+        elif b[0] == "b":
+            Qb = top(b[1])
+        else:
+            _, grav, al, be, Tn, Sn = b
+            Qb = float(grav) * (float(al) * top(Tn) - float(be) * top(Sn))
+        dz = g.Δzᵃᵃᶜ[g.Nz - 1]
+        w3 = np.maximum(0.0, Qb) * dz
+        us = np.sqrt(np.sqrt(Qu * Qu + Qv * Qv))
+        s = catke.surface_TKE_flux
+        Qe = -catke.CD * (s.CWu_star * (us * us * us) + s.CWw_delta * w3)
+        return Qb, Qe
+
+    def _send_catke(self, catke, Qb):
+        parts = closure_parts(self.closure)
+        alone = not isinstance(self.closure, tuple)
+        kinds = [] if alone else [_KIND_CODE[CATKEVerticalDiffusivity]] + [_KIND_CODE[k] for k in parts if k is not CATKEVerticalDiffusivity]
+        m = np.array(catke.mixing_length.values())
+        PD = C.POINTER(C.c_double)
+        g = self.grid
+        qb = None if Qb is None or (np.ndim(Qb) == 0 and Qb == 0) else np.ascontiguousarray(np.broadcast_to(Qb, (g.Nx, g.Ny)).ravel(order="F"))
+        check(self.lib.ocn_hydro_set_catke(self.h, 1, catke.DISCRETIZATIONS.index(catke.time_discretization), catke.CD, m.ctypes.data_as(PD),
+                                           list(self.tracers).index("e"), None if qb is None else qb.ctypes.data_as(PD),
+                                           0 if qb is None else qb.size, len(kinds), (C.c_int32 * max(1, len(kinds)))(*kinds)), g.ctx.h)
+
+    def _check_catke(self, catke, parts, closure):
+        """the refusals of a CATKEVerticalDiffusivity in this model, before anything is set (ValueError, each with its reason)"""
+        name = "CATKEVerticalDiffusivity"
+        if "e" not in self.tracers:
+            raise ValueError(f"Tracers must contain :e to represent turbulent kinetic energy for `{name}`.")
+        catke.check()
+        if isinstance(closure, tuple) and len(closure) > 3:
+            raise ValueError(f"{name} in a tuple of {len(closure)} closures: the reference has no shear_production method beyond three")
+        for other in (ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity, IsopycnalSkewSymmetricDiffusivity):
+            if other in parts:
+                raise ValueError(f"{name} next to a {other.__name__} is out of scope: one set of column coefficients per model")
+        self._catke_fluxes(catke, getattr(self, "boundary_conditions", {}))         # a top LinearDrag is refused here
 
     def _coefficient_tables(self, closure, f, is_nu, what):
         """the two (rows, Nz) location tables of the function coefficient f of `closure`: rows are those of the grid's per-row metric
@@ -974,11 +1143,18 @@ class HydrostaticState:
         HorizontalDivergenceScalarDiffusivity, HorizontalDivergenceScalarBiharmonicDiffusivity, VerticalScalarDiffusivity,
         ConvectiveAdjustmentVerticalDiffusivity, RiBasedVerticalDiffusivity (at most one of the last two; at most one non-zero nu among
         the two closures of the Laplacian order and among the two of the biharmonic order); explicit terms summed in tuple order.
-        Function coefficients are evaluated here, once; `horizontal_coefficient_tables` keeps what was sent"""
+        A CATKEVerticalDiffusivity needs the tracer "e", stands alone or in a tuple of up to three closures without CAVD, RBVD and the
+        isopycnal closure, and is summed first wherever it stands (the reference sorts it first); its surface fluxes follow the boundary
+        conditions, set before or after.  Function coefficients are evaluated here, once; `horizontal_coefficient_tables` keeps what
+        was sent"""
         parts = closure_parts(closure)
         names = list(self.tracers)
         PD = C.POINTER(C.c_double)
         zero = _ScalarClosure()
+        catke = parts.get(CATKEVerticalDiffusivity)
+        had_catke = CATKEVerticalDiffusivity in closure_parts(getattr(self, "closure", None))
+        if catke is not None:
+            self._check_catke(catke, parts, closure)
         iso = parts.get(IsopycnalSkewSymmetricDiffusivity)
         if iso is not None:
             self._check_isopycnal(iso, parts)
@@ -1015,6 +1191,8 @@ class HydrostaticState:
             # the isopycnal closure's term is a pass of its own: the other setters take the tuple without it
             kinds = [_KIND_CODE[k] for k in parts if k is kind or k is not IsopycnalSkewSymmetricDiffusivity] if kind in parts else []
             return len(kinds), (C.c_int32 * max(1, len(kinds)))(*kinds)
+        if catke is None:          # switched off first, so that the closures it refuses next to it can come on
+            check(self.lib.ocn_hydro_set_catke(self.h, 0, 0, 0.0, None, -1, None, 0, 0, None), self.grid.ctx.h)
 
         def set_iso():
             c = iso or IsopycnalSkewSymmetricDiffusivity()
@@ -1047,6 +1225,11 @@ class HydrostaticState:
         if iso is not None:
             set_iso()
         self.closure = closure
+        # the top flux of e and the surface buoyancy flux come from the boundary conditions: set in either order
+        if catke is not None and not hasattr(self, "boundary_conditions"):
+            self._send_catke(catke, None)
+        elif catke is not None or had_catke:
+            self.set_boundary_conditions(self.boundary_conditions)
 
     def _check_isopycnal(self, iso, parts):
         """the refusals of an IsopycnalSkewSymmetricDiffusivity in this model, before anything is set (ValueError, each with its reason)"""
@@ -1073,13 +1256,15 @@ class HydrostaticState:
     def diffusivity_fields(self):
         """{"kappa": HField, "nu": HField} of the ConvectiveAdjustmentVerticalDiffusivity or RiBasedVerticalDiffusivity switched on
         last ((Center, Center, Face), or (Center, Center, Center) for a RiBasedVerticalDiffusivity at Center; set by update_state), plus
-        "eps_R33" (Center, Center, Face) while an IsopycnalSkewSymmetricDiffusivity is on; None before any of them was first switched
+        "eps_R33" (Center, Center, Face) while an IsopycnalSkewSymmetricDiffusivity is on, plus "Ku", "Kc", "Ke" (Center, Center, Face)
+        and "Le" (Center, Center, Center) once a CATKEVerticalDiffusivity was switched on; None before any of them was first switched
         on"""
         hk, hn = self.lib.ocn_hydro_diffusivity_field(self.h, 0), self.lib.ocn_hydro_diffusivity_field(self.h, 1)
         he = self.lib.ocn_hydro_isopycnal_field(self.h, 0)
-        if not hk and not he:
+        hc = [self.lib.ocn_hydro_catke_field(self.h, q) for q in range(4)]
+        if not hk and not he and not hc[0]:
             return None
-        handles = {"kappa": hk, "nu": hn, "eps_R33": he}
+        handles = {"kappa": hk, "nu": hn, "eps_R33": he, "Ku": hc[0], "Kc": hc[1], "Ke": hc[2], "Le": hc[3]}
         cached = getattr(self, "_diffusivity_fields", None)
         if cached is None or {n: (cached[n].h.value if n in cached else None) for n in handles} != handles:
             fields = {}
@@ -1090,6 +1275,9 @@ class HydrostaticState:
                 fields = {"kappa": HField(self.grid, (Center, Center, lz), handle=hk), "nu": HField(self.grid, (Center, Center, lz), handle=hn)}
             if he:
                 fields["eps_R33"] = HField(self.grid, (Center, Center, Face), handle=he)
+            if hc[0]:
+                for n, hq in zip(("Ku", "Kc", "Ke", "Le"), hc):
+                    fields[n] = HField(self.grid, (Center, Center, Center if n == "Le" else Face), handle=hq)
             self._diffusivity_fields = fields
         return self._diffusivity_fields
 

@@ -532,6 +532,28 @@ int ocn_hydro_set_isopycnal_diffusivity(ocn_hydro* h, int32_t discretization, do
 /* diffusivity_fields of the isopycnal closure: which 0 eps_R33, the tapered 33 component of the rotation tensor, a (Center, Center,
  * Face) field owned by the handle (faces 1..Nz of the grid's columns, x / y halos filled, nothing in z); NULL while the closure is off */
 ocn_hfield* ocn_hydro_isopycnal_field(ocn_hydro* h, int32_t which);
+/* closure = CATKEVerticalDiffusivity(VerticallyImplicitTimeDiscretization(); CD, mixing_length) (TurbulenceClosures/
+ * turbulence_closure_implementations/CATKEVerticalDiffusivities/), the reference's TKE-based boundary-layer scheme.  The tracer
+ * e_index is the turbulent kinetic energy e.  update_state! computes K^u, K^c, K^e at faces 1..Nz (nothing is filled in z: face
+ * Nz + 1 stays zero) and L^e = -CD sqrt|e| / Iz(l_e) at the centres in one launch; u and v are solved with K^u, the
+ * tracers with K^c, e with K^e; G^n of e gets shear production and buoyancy flux; G^n of u and v the w-shear term of a vertically
+ * implicit closure.  L^e enters the diagonal of e's solve (1 - dt L - upper - lower) when the closure stands alone (ntuple 0): in a
+ * tuple the reference's diagonal has no linear term.  mixing_length: the 25 numbers of MixingLength in the order Cb, Cs, Cbu, Cbc, Cbe,
+ * Csu, Csc, Cse, Cdu, Cdc, Cde, CAu, CAc, CAe, CASu, CASc, CASe, CKu-, CKur, CKc-, CKcr, CKe-, CKer, CKRiw, CKRic.  top_buoyancy_flux:
+ * the static Q^b(i, j) of the convective length, Nx * Ny numbers of this grid's (band's) columns, or n_flux 0 for zero.  The top flux
+ * of e (top_tke_flux) is a condition like any other: set it with ocn_hydro_set_flux_bc.  `tuple` as for
+ * ocn_hydro_set_convective_adjustment, with this closure first, where the reference sorts it.  on 0 switches the closure off.
+ * OCN_EUNSUPPORTED: discretization 1 (the reference's explicit dissipation silently evaluates to zero), a tuple of more than three
+ * closures (no shear_production method beyond three), a tuple or handle with a ConvectiveAdjustmentVerticalDiffusivity,
+ * RiBasedVerticalDiffusivity or IsopycnalSkewSymmetricDiffusivity (their setters refuse the converse).  OCN_EINVAL: no tracer e, two
+ * CATKEs, a parameter where the reference would compute 0 * Inf or divide by zero (Cb, Cs > 0 with Inf legal; the per-field Cb, Cs,
+ * Cdelta, CK-, CKRiw finite and > 0; the others finite and >= 0; CKRic finite), a flux array of another size. */
+enum { OCN_CLOSURE_CATKE = 8 };
+int ocn_hydro_set_catke(ocn_hydro* h, int32_t on, int32_t discretization, double CD, const double* mixing_length, int32_t e_index,
+                        const double* top_buoyancy_flux, int64_t n_flux, int32_t ntuple, const int32_t* tuple);
+/* diffusivity_fields of the CATKE closure: which 0 K^u, 1 K^c, 2 K^e ((Center, Center, Face) parents; the x / y halos of K^u as the
+ * reference's fills leave them), 3 L^e ((Center, Center, Center)); owned by the handle; NULL before the closure was first switched on */
+ocn_hfield* ocn_hydro_catke_field(ocn_hydro* h, int32_t which);
 /* calculate_tendencies!(model) (calculate_hydrostatic_free_surface_tendencies.jl:15-160): G^n of u, v and every tracer over the
  * grid's cells, from the state update_state! left (filled halos, w, pHY') */
 int ocn_hydro_calculate_tendencies(ocn_hydro* h);
