@@ -128,8 +128,9 @@ OCN_DEVFN void sto_once(double* base, unsigned boff, double v) {
 // boundary buffer (topologically_conditional_interpolation.jl:46-79).  REST: G^n arrives holding everything but advection
 // (closure, Coriolis, pressure gradient, boundary fluxes from the general kernels) and leaves as the full tendency;
 // walls in x / y are runtime flags of the REST variants (the same fallbacks on the x / y stencils).
-template <int ADV, int BX, int BY, bool XT, int DMA, bool VISC, bool ZB, bool REST, bool NT>
+template <int ADV, int BX, int BY, bool XT, int DMA, bool VISC, bool ZB, bool REST, bool NT, bool ASEL = false>
 __global__ void __launch_bounds__(BX* BY) k_tend4(GridDev g, FusedArgs a) {
+  static_assert(!ASEL || (!XT && !VISC && !ZB && !REST), "k_tend4: address-selected stencils are built for the inviscid all-in-one kernel on complete rows only");
   constexpr int T = BX * BY, NR = BY + 5, SX = BX + 6;
   constexpr int WV = BX < OCN_WAVE ? BX : OCN_WAVE;   // lanes of a wave that lie in one row
   constexpr int NW = BX / WV;                         // waves per row
@@ -348,9 +349,23 @@ __global__ void __launch_bounds__(BX* BY) k_tend4(GridDev g, FusedArgs a) {
                                                : sym_v(SLB(f, 3, 1), SLB(f, 3, 2), SLB(f, 3, 3), SLB(f, 3, 4)))
 #define YSYM(f, idx) ((wy && !in_sym(idx, g.Ny)) ? 0.5 * (SLB(f, 2, 3) + SLB(f, 3, 3)) \
                                                : sym_v(SLB(f, 1, 3), SLB(f, 2, 3), SLB(f, 3, 3), SLB(f, 4, 3)))
+    // ASEL: the five values of the upwind stencil sit at P[q w] (ut > 0) or P[(5 - q) w] of the six-point footprint at P.
+    // Select the ADDRESS -- one select for the base, one for the signed stride, four integer adds; the field / row / column
+    // offset F stays an immediate of the LDS reads -- instead of reading six values and selecting five of them (ten
+    // v_cndmask_b32 per reconstruction).  Same values, same arithmetic: bitwise the same flux.  256^3: 801 -> 774 VALU
+    // instructions per 64 cells, 507 -> 492 us (profiles/tend4_spread_notes.md).
+    auto rec_a = [&](const double* P, int F, int w, double ut) {
+      const bool pos = ut > 0.0;
+      const double* b0 = P + (pos ? 0 : 5 * w);
+      const int st = pos ? w : -w;
+      const double *b1 = b0 + st, *b2 = b1 + st, *b3 = b2 + st, *b4 = b3 + st;
+      return recon5<ADV>(b0[F], b1[F], b2[F], b3[F], b4[F], pos);
+    };
 #define XREC(f, ut, idx) ((wx && !in_rec((ut) > 0.0, idx, g.Nx)) ? 0.5 * (SLB(f, 3, 2) + SLB(f, 3, 3)) \
+                              : ASEL ? rec_a(S, (f) * NR * SX + 3 * SX, 1, ut)                                               \
                               : rec_v(SLB(f, 3, 0), SLB(f, 3, 1), SLB(f, 3, 2), SLB(f, 3, 3), SLB(f, 3, 4), SLB(f, 3, 5), ut))
 #define YREC(f, ut, idx) ((wy && !in_rec((ut) > 0.0, idx, g.Ny)) ? 0.5 * (SLB(f, 2, 3) + SLB(f, 3, 3)) \
+                              : ASEL ? rec_a(S, (f) * NR * SX + 3, SX, ut)                                                   \
                               : rec_v(SLB(f, 0, 3), SLB(f, 1, 3), SLB(f, 2, 3), SLB(f, 3, 3), SLB(f, 4, 3), SLB(f, 5, 3), ut))
     // ---- bottom-face fluxes of level k (= top-face fluxes of level k-1), then the update of level k-1 --------------------
     if (full) {
@@ -1018,13 +1033,16 @@ bool fused_available(const ocn_model* m) {
   return true;
 }
 
+static bool tend4_asel(const ocn_model* m, bool plain);
+
 void fused_describe(const ocn_model* m, char* buf, size_t n) {
   const char* why = tiled_blocker(m);
   if (m->fast_path) {
     const size_t halo_bytes = (size_t)(3 + m->nt) * m->gd.Hz * m->u.sz * sizeof(double);
     const bool ov = m->g->dist && m->gd.Nz > 2 * m->gd.Hz + 2 &&
                     (m->knob_overlap >= 0 ? m->knob_overlap != 0 : (m->ctx->nranks > 1 && halo_bytes >= ((size_t)8 << 20)));
-    snprintf(buf, n, "all-in-one periodic path: k_tend4 + fused Poisson passes + k_project%s",
+    const bool asel = tend4_asel(m, !(m->d.closure == OCN_CLOSURE_SCALAR && m->d.nu != 0.0));
+    snprintf(buf, n, "all-in-one periodic path: k_tend4%s + fused Poisson passes + k_project%s", asel ? " (address-selected stencils)" : "",
              !m->g->dist ? "" : ov ? "; z-slabs, halo planes travel under the next interior tendency launch"
                                    : "; z-slabs, halo exchange on the model's stream");
   }
@@ -1058,6 +1076,7 @@ struct FusedShape {
   int bx, by;
   bool wide, small;
   int dma;       // slab staged by global_load_lds: 1 row by row, 2 one chunk per field (rows with the slab's pitch); 0: registers
+  bool asel;     // k_tend4 reads its x / y upwind stencils from selected addresses (tend4_asel)
   dim3 blk, grd;
 };
 
@@ -1070,6 +1089,8 @@ struct FusedShape {
 //   OCNHIP_NO_GRAPH=1     general path: issue every launch of a step from the host instead of replaying a hipGraph
 //   OCNHIP_LOCALITY=0     k_tend4 with the default cache policy on every stream (tests, same-build A/B; see the kernel's note)
 //   OCNHIP_NO_SMAG_TILED=1  SmagorinskyLilly: the one-thread-per-cell nu_e kernel where k_smag_nu would apply (tests, A/B)
+//   OCNHIP_TEND4_VSEL=1   k_tend4 reads six stencil values and selects five where the address-selected form exists (tests,
+//                         same-build A/B; see rec_a in the kernel)
 void fused_read_knobs(ocn_model* m) {
   auto env = [](const char* n, int def) { const char* e = getenv(n); return e ? atoi(e) : def; };
   m->knob_fused_xt = env("OCNHIP_FUSED_XT", 0);
@@ -1084,9 +1105,22 @@ void fused_read_knobs(ocn_model* m) {
   { const char* e = getenv("OCNHIP_PRIO"); m->knob_prio = e ? (int)strtol(e, nullptr, 0) : 0x20FF; }
   { const char* e = getenv("OCNHIP_LOCALITY"); m->knob_locality = e ? atoi(e) : 1; }
   m->knob_no_smag_tiled = env("OCNHIP_NO_SMAG_TILED", 0);
+  m->knob_tend4_vsel = env("OCNHIP_TEND4_VSEL", 0);
 }
 
-static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
+// address-selected stencils: the inviscid all-in-one kernel (`plain`) on complete rows of 129 ... 256 columns (256 x 4
+// threads; 16 x 4 in the host emulation)
+static bool tend4_asel(const ocn_model* m, bool plain) {
+  const GridDev& gd = m->gd;
+  if (!plain || m->knob_tend4_vsel || gd.Nx > 256 || gd.xb || (m->knob_fused_xt == 1 && gd.Nx <= 57 * 4)) return false;
+#ifdef OCN_HOST_EMU
+  return gd.Nx <= 16;
+#else
+  return gd.Nx > 128;
+#endif
+}
+
+static FusedShape fused_shape(const ocn_model* m, FusedArgs& a, bool plain = false) {
   const GridDev& gd = m->gd;
   FusedShape f;
   f.small = m->knob_fused_xt == 1 && gd.Nx <= 57 * 4;   // test shape: 64 x 4 threads, up to 56 output columns, >= 2 tiles
@@ -1137,6 +1171,7 @@ static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
 #ifdef OCN_HOST_EMU
   nseg = total >= 3 ? 3 : 1;                      // one OS thread per emulated GPU thread: few workgroups, still several segments
 #endif
+  f.asel = tend4_asel(m, plain);
   f.blk = dim3(f.bx, f.by, 1);
   f.grd = dim3(nseg, 1, 1);
   // 16-byte pieces: a slab row starts at parent column Hx - 3 + i0 (i0 = x-tile origin, even), rows are sy doubles apart,
@@ -1154,6 +1189,23 @@ static FusedShape fused_shape(const ocn_model* m, FusedArgs& a) {
 #define FUSED_T4(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV)                                                                   \
   { if (m->knob_locality) FUSED_T4N(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV, true)                           \
     else FUSED_T4N(ADVV, BXV, BYV, XTV, VISCV, ZBV, RESTV, false) }
+// the inviscid all-in-one kernel with address-selected stencils (f.asel: complete rows, 256 x 4 / emulated 16 x 4 threads)
+#define FUSED_T4AN(ADVV, BXV, NTV)                                                                                         \
+  { if (f.dma == 2) ocn_launch_sync(k_tend4<ADVV, BXV, 4, false, 2, false, false, false, NTV, true>, f.grd, f.blk, s, m->gd, a);    \
+    else if (f.dma) ocn_launch_sync(k_tend4<ADVV, BXV, 4, false, 1, false, false, false, NTV, true>, f.grd, f.blk, s, m->gd, a);   \
+    else ocn_launch_sync(k_tend4<ADVV, BXV, 4, false, 0, false, false, false, NTV, true>, f.grd, f.blk, s, m->gd, a); }
+#define FUSED_T4A(ADVV, BXV) { if (m->knob_locality) FUSED_T4AN(ADVV, BXV, true) else FUSED_T4AN(ADVV, BXV, false) }
+#ifdef OCN_HOST_EMU
+#define FUSED_ASEL_BX 16
+#else
+#define FUSED_ASEL_BX 256
+#endif
+#define FUSED_ASEL_BY_SCHEME                                        \
+  switch (m->d.advection) {                                         \
+    case ADV_WENO_Z: FUSED_T4A(ADV_WENO_Z, FUSED_ASEL_BX) break;    \
+    case ADV_WENO_JS: FUSED_T4A(ADV_WENO_JS, FUSED_ASEL_BX) break;  \
+    default: FUSED_T4A(ADV_U5, FUSED_ASEL_BX) break;                \
+  }
 #ifdef OCN_HOST_EMU
 #define FUSED_EMU16(ADVV, VISCV, ZBV, RESTV)                                                                               \
   if (f.bx == 16 && f.small) FUSED_T4(ADVV, 16, 4, true, VISCV, ZBV, RESTV)                                                \
@@ -1202,10 +1254,12 @@ void launch_fused_tend_step(ocn_model* m, double dt, double cn, double cm, int u
   a.zhi2 = zhi2;
   if (a.zhi <= a.zlo) return;
   a.nu = m->d.closure == OCN_CLOSURE_SCALAR ? m->d.nu : 0.0;
-  const FusedShape f = fused_shape(m, a);
+  const FusedShape f = fused_shape(m, a, a.nu == 0.0);
   hipStream_t s = m->ctx->stream;
   if (a.nu != 0.0) {
     FUSED_BY_SCHEME(true, false, false)
+  } else if (f.asel) {
+    FUSED_ASEL_BY_SCHEME
   } else {
     FUSED_BY_SCHEME(false, false, false)
   }

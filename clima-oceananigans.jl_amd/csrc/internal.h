@@ -145,6 +145,7 @@ struct ocn_model {
   bool pnhs_halo_stale = false;
   int knob_xfft_team = 0;    // OCNHIP_XFFT_TEAM=1: the fused rhs + x transform loads in team order (the older variant; tests)
   int knob_graph = 1;        // OCNHIP_NO_GRAPH=1 clears it (model creation)
+  int knob_tend4_vsel = 0;   // OCNHIP_TEND4_VSEL=1: k_tend4 selects stencil values, not addresses, everywhere (tests, A/B)
   int knob_locality = 1;     // OCNHIP_LOCALITY=0: k_tend4's once-touched streams (G^- loads, G^n / U* stores) keep the default cache policy
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
