@@ -17,6 +17,7 @@ thread_local int g_ocn_capturing = 0, g_ocn_capture_poison = 0;
 
 static char g_last_error[512] = {0};
 static int pnhs_refresh(ocn_model* m);
+static int pnhs_materialize(ocn_model* m);
 
 void ocn_set_error(ocn_ctx* ctx, const char* fmt, ...) {
   va_list ap;
@@ -512,6 +513,7 @@ static int pressure_correction(ocn_model* m, double dt) {
   // pressure_correction.jl:10-23
   int rc = fill_velocities_tracers(m, false);
   if (rc) return rc;
+  m->pnhs_deferred = false;   // the solve overwrites the solver's buffer and writes a complete new pNHS (halos: right below)
   if ((rc = poisson_solve(m, dt))) return rc;
   Field* fs[1] = {&m->pNHS};
   return fill_fields(m, fs, 1);
@@ -563,6 +565,15 @@ static int pnhs_refresh(ocn_model* m) {
   m->pnhs_halo_stale = false;
   Field* fs[1] = {&m->pNHS};
   return comm_halo_exchange_z(m, fs, 1);
+}
+// deferred store of pNHS (see ocn_model::pnhs_deferred): the field and all its periodic images from the solver's real buffer,
+// on the model's stream.  Runs before every reader of pNHS and before everything that overwrites the solver's buffers outside
+// fused_substep; never inside a captured step.
+static int pnhs_materialize(ocn_model* m) {
+  if (!m->pnhs_deferred) return OCN_OK;
+  m->pnhs_deferred = false;
+  launch_pressure_images(m, poisson_rhs_buffer(m->solver));
+  return OCN_OK;
 }
 static int halo_settle_others(ocn_model* m) {
   for (ocn_model* o : m->ctx->models)
@@ -616,7 +627,9 @@ static int fused_substep(ocn_model* m, double dt_full, double cn, double cm, int
   // p of the level below the slab, for d_z p at the first level: computed by this rank with one more level of the Green's-function
   // convolution (poisson.hip pbelow), or received from the lower neighbour
   if (m->g->dist && !poisson_local_phi_below(m) && (rc = fused_exchange_phi(m, poisson_rhs_buffer(m->solver)))) return rc;
-  launch_project(m, dt_stage, poisson_rhs_buffer(m->solver));
+  const bool lazy = pnhs_lazy(m);
+  launch_project(m, dt_stage, poisson_rhs_buffer(m->solver), !lazy);
+  m->pnhs_deferred = lazy;   // a later (sub)step simply supersedes it: only the last solve's pressure survives, as with the store
   if (m->g->dist) {
     ocn_ctx* c = m->ctx;
     // Worth it when the transfer it hides is longer than what the split costs (0.05-0.07 ms): 19 MB per direction at config 4
@@ -794,6 +807,7 @@ static uint64_t step_key(const ocn_model* m, double dt, int force_euler, std::ve
   words.push_back(m->iteration == 0);
   words.push_back(m->gn_alias_gm);
   words.push_back(m->pred_active);
+  words.push_back(pnhs_lazy(m));   // which k_project the step launches
   auto fp = [&](const Field& f) { words.push_back((uint64_t)(uintptr_t)f.d); };
   fp(m->u); fp(m->v); fp(m->w); fp(m->us); fp(m->vs); fp(m->ws);
   for (int t = 0; t < m->nt; ++t) { fp(m->tr[t]); fp(m->trs[t]); }
@@ -1151,6 +1165,12 @@ int ocn_field_shape(const ocn_model* m, int field_id, int32_t total[3], int32_t 
 
 void* ocn_field_device_ptr(ocn_model* m, int field_id) {
   if (m) halo_settle(m);   // work the caller enqueues on ocn_stream() after this call sees complete halos
+  if (m && field_id == OCN_F_PNHS) {
+    // the array is current now, and from here on the library cannot know when it is read: every projection stores it again
+    // (the step graphs are keyed on the form, so the captured lazy ones are not replayed any more)
+    pnhs_materialize(m);
+    if (pnhs_lazy(m)) m->pnhs_escaped = true;
+  }
   Field* f = model_field(m, field_id);
   return f ? f->d : nullptr;
 }
@@ -1220,6 +1240,7 @@ int ocn_field_upload(ocn_model* m, int field_id, const double* host) {
   if (m && field_id >= OCN_F_GN && field_id < OCN_F_GN + OCN_NF && materialize_gn(m)) return OCN_EHIP;
   Field* f = model_field(m, field_id);
   if (!f || !host) return OCN_EINVAL;
+  if (field_id == OCN_F_PNHS) m->pnhs_deferred = false;   // the whole parent array is replaced: the deferred pressure is superseded
   return parent_upload(m->ctx, f, host);
 }
 
@@ -1227,6 +1248,7 @@ int ocn_field_download(const ocn_model* m, int field_id, double* host) {
   if (m && halo_settle(const_cast<ocn_model*>(m))) return OCN_EHIP;
   if (m && field_id == OCN_F_PNHS)
     if (int rc = pnhs_refresh(const_cast<ocn_model*>(m))) return rc;
+  if (m && field_id == OCN_F_PNHS && pnhs_materialize(const_cast<ocn_model*>(m))) return OCN_EHIP;
   Field* f = model_field(const_cast<ocn_model*>(m), field_id);
   if (!f || !host) return OCN_EINVAL;
   return parent_download(m->ctx, f, host);
@@ -1302,6 +1324,7 @@ int ocn_field_parent_download(const ocn_field* f, double* host) {
 int ocn_field_set_interior(ocn_model* m, int field_id, const double* host) {
   if (m && halo_settle(m)) return OCN_EHIP;
   if (m && field_id >= OCN_F_GN && field_id < OCN_F_GN + OCN_NF && materialize_gn(m)) return OCN_EHIP;
+  if (m && field_id == OCN_F_PNHS && pnhs_materialize(m)) return OCN_EHIP;   // only the interior is rewritten here
   Field* f = model_field(m, field_id);
   if (!f || !host) return OCN_EINVAL;
   int32_t it[3];
@@ -1317,6 +1340,7 @@ int ocn_field_set_interior(ocn_model* m, int field_id, const double* host) {
 
 int ocn_field_get_interior(const ocn_model* m, int field_id, double* host) {
   if (m && halo_settle(const_cast<ocn_model*>(m))) return OCN_EHIP;
+  if (m && field_id == OCN_F_PNHS && pnhs_materialize(const_cast<ocn_model*>(m))) return OCN_EHIP;
   Field* f = model_field(const_cast<ocn_model*>(m), field_id);
   if (!f || !host) return OCN_EINVAL;
   int32_t it[3];
@@ -1343,6 +1367,7 @@ int ocn_fill_halos(ocn_model* m, uint32_t mask) {
     if (mask & (1u << (8 + t))) fs[n++] = &m->tr[t];
   // fields of one call share one batched launch; aux fields (pressures) use their own z conditions
   if (mask & (1u << 4)) m->pnhs_halo_stale = false;   // filled right here
+  if ((mask & (1u << 4)) && pnhs_materialize(m)) return OCN_EHIP;
   return api_ret(m->ctx, fill_fields(m, fs, n));
 }
 
@@ -1385,6 +1410,7 @@ int ocn_pressure_correction(ocn_model* m, double dt) { return m ? api_ret(m->ctx
 int ocn_pressure_correct_velocities(ocn_model* m, double dt) {
   if (!m) return OCN_EINVAL;
   if (halo_settle(m)) return OCN_EHIP;
+  if (pnhs_materialize(m)) return OCN_EHIP;
   launch_pcorrect(m, dt);
   return api_ret(m->ctx, OCN_OK);
 }
@@ -1392,6 +1418,7 @@ int ocn_pressure_correct_velocities(ocn_model* m, double dt) {
 int ocn_poisson_solve_host(ocn_model* m, const double* rhs, double* phi) {
   if (!m || !rhs || !phi) return OCN_EINVAL;
   if (halo_settle(m)) return OCN_EHIP;
+  if (pnhs_materialize(m)) return OCN_EHIP;   // the solve below runs in the buffer the deferred pressure lives in
   size_t n = (size_t)m->g->N[0] * m->g->N[1] * m->g->N[2];
   double *a = nullptr, *b = nullptr;
   OCN_HIP_CHECK(m->ctx, hipMalloc((void**)&a, n * sizeof(double)));

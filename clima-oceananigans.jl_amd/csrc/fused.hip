@@ -12,7 +12,8 @@
 //   k_project   : copy_real_component! + _pressure_correct_velocities! + the periodic halo fills of
 //                 update_state! / calculate_pressure_correction!, all in one pass: each thread writes its
 //                 interior value and its periodic images             (pressure_correction.jl:34-40,
-//                 fill_halo_regions_periodic.jl:37-65)
+//                 fill_halo_regions_periodic.jl:37-65); <false>: without copy_real_component!, which
+//   k_pressure_images does (with the images of pNHS) when the field is asked for
 //
 // Design of the tendency kernel (why it looks the way it does):
 //   * it is FP64-VALU bound, not HBM bound: one WENO reconstruction is ~60 DP operations and the reference
@@ -733,6 +734,9 @@ OCN_DEVFN void store_images(const GridDev& g, double* f, int i, int j, int k, do
       for (int c1 = 0; c1 < nx; ++c1) f[c + ox[c1] + oy[c2] + oz[c3]] = val;
 }
 
+// STORE_P = false: the pressure stays in the solver's buffer and k_pressure_images writes pNHS when somebody asks for it
+// (ocn_model::pnhs_deferred); u, v, w come out of the same loads and the same arithmetic either way.
+template <bool STORE_P = true>
 __global__ void k_project(GridDev g, ProjArgs a) {
   int i, j;
   ocn_cell_ij(i, j);
@@ -755,7 +759,16 @@ __global__ void k_project(GridDev g, ProjArgs a) {
   store_images(g, a.u, i, j, k, un, a.zwrap);
   store_images(g, a.v, i, j, k, vn, a.zwrap);
   store_images(g, a.w, i, j, k, wn, a.zwrap);
-  store_images(g, a.p, i, j, k, p0, a.zwrap);
+  if (STORE_P) store_images(g, a.p, i, j, k, p0, a.zwrap);
+}
+
+// the store the lazy projection left out: pNHS and all its periodic images from the solver's compact (Nx, Ny, Nz) buffer
+__global__ void k_pressure_images(GridDev g, const double* __restrict__ phi, double* __restrict__ p, int zwrap) {
+  int i, j;
+  ocn_cell_ij(i, j);
+  const int k = blockIdx.z;
+  if (i >= g.Nx || j >= g.Ny || k >= g.Nz) return;
+  store_images(g, p, i, j, k, phi[i + (long)g.Nx * (j + (long)g.Ny * k)], zwrap);
 }
 
 // ---- passive tracers on the fast path: calculate_Gc! + time-stepper update in one pass ---------------------------
@@ -1042,8 +1055,11 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
     const bool ov = m->g->dist && m->gd.Nz > 2 * m->gd.Hz + 2 &&
                     (m->knob_overlap >= 0 ? m->knob_overlap != 0 : (m->ctx->nranks > 1 && halo_bytes >= ((size_t)8 << 20)));
     const bool asel = tend4_asel(m, !(m->d.closure == OCN_CLOSURE_SCALAR && m->d.nu != 0.0));
-    snprintf(buf, n, "all-in-one periodic path: k_tend4%s + fused Poisson passes + k_project%s", asel ? " (address-selected stencils)" : "",
-             !m->g->dist ? "" : ov ? "; z-slabs, halo planes travel under the next interior tendency launch"
+    const char* pform = m->g->dist ? "" : pnhs_lazy(m) ? " (pressure written on demand)"
+                        : m->pnhs_escaped ? " (pressure stored by every projection: its device pointer was handed out)"
+                                          : " (pressure stored by every projection)";
+    snprintf(buf, n, "all-in-one periodic path: k_tend4%s + fused Poisson passes + k_project%s%s", asel ? " (address-selected stencils)" : "",
+             pform, !m->g->dist ? "" : ov ? "; z-slabs, halo planes travel under the next interior tendency launch"
                                    : "; z-slabs, halo exchange on the model's stream");
   }
   else if (m->bz_fast) snprintf(buf, n, "tiled advection + update (k_tend4, REST) on top of the %s other terms",
@@ -1091,6 +1107,8 @@ struct FusedShape {
 //   OCNHIP_NO_SMAG_TILED=1  SmagorinskyLilly: the one-thread-per-cell nu_e kernel where k_smag_nu would apply (tests, A/B)
 //   OCNHIP_TEND4_VSEL=1   k_tend4 reads six stencil values and selects five where the address-selected form exists (tests,
 //                         same-build A/B; see rec_a in the kernel)
+//   OCNHIP_EAGER_PRESSURE=1  every projection of the all-in-one path stores pNHS (for callers who read the pressure after every
+//                         step; tests, same-build A/B; see ocn_model::pnhs_deferred)
 void fused_read_knobs(ocn_model* m) {
   auto env = [](const char* n, int def) { const char* e = getenv(n); return e ? atoi(e) : def; };
   m->knob_fused_xt = env("OCNHIP_FUSED_XT", 0);
@@ -1106,6 +1124,7 @@ void fused_read_knobs(ocn_model* m) {
   { const char* e = getenv("OCNHIP_LOCALITY"); m->knob_locality = e ? atoi(e) : 1; }
   m->knob_no_smag_tiled = env("OCNHIP_NO_SMAG_TILED", 0);
   m->knob_tend4_vsel = env("OCNHIP_TEND4_VSEL", 0);
+  m->knob_eager_pressure = env("OCNHIP_EAGER_PRESSURE", 0);
 }
 
 // address-selected stencils: the inviscid all-in-one kernel (`plain`) on complete rows of 129 ... 256 columns (256 x 4
@@ -1353,7 +1372,7 @@ void launch_rhs_wrap(ocn_model* m, double dt, double* rhs) {
              (const double*)m->ws.interior(), 1.0 / dt, m->g->dist ? 0 : 1, rhs);
 }
 
-void launch_project(ocn_model* m, double dt, const double* phi) {
+void launch_project(ocn_model* m, double dt, const double* phi, bool store_p) {
   ProfScope ps(m->ctx, "pcorrect");
   const GridDev& g = m->gd;
   ProjArgs a;
@@ -1364,7 +1383,15 @@ void launch_project(ocn_model* m, double dt, const double* phi) {
   a.zwrap = m->g->dist ? 0 : 1;
   a.phi_below = poisson_local_phi_below(m) ? poisson_phi_below(m) : m->phi_below;
   dim3 b(256, 1, 1), gr((g.Nx + b.x - 1) / b.x, (g.Ny + b.y - 1) / b.y, g.Nz);
-  ocn_launch(k_project, gr, b, m->ctx->stream, g, a);
+  if (store_p) ocn_launch(k_project<true>, gr, b, m->ctx->stream, g, a);
+  else ocn_launch(k_project<false>, gr, b, m->ctx->stream, g, a);
+}
+
+void launch_pressure_images(ocn_model* m, const double* phi) {
+  ProfScope ps(m->ctx, "copy_pressure");
+  const GridDev& g = m->gd;
+  dim3 b(256, 1, 1), gr((g.Nx + b.x - 1) / b.x, (g.Ny + b.y - 1) / b.y, g.Nz);
+  ocn_launch(k_pressure_images, gr, b, m->ctx->stream, g, phi, m->pNHS.interior(), m->g->dist ? 0 : 1);
 }
 
 // ---- slab runs: the two one-plane exchanges the fused path needs besides the z-halo exchange -----------------

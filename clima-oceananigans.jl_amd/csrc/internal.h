@@ -147,6 +147,14 @@ struct ocn_model {
   int knob_graph = 1;        // OCNHIP_NO_GRAPH=1 clears it (model creation)
   int knob_tend4_vsel = 0;   // OCNHIP_TEND4_VSEL=1: k_tend4 selects stencil values, not addresses, everywhere (tests, A/B)
   int knob_locality = 1;     // OCNHIP_LOCALITY=0: k_tend4's once-touched streams (G^- loads, G^n / U* stores) keep the default cache policy
+  // Single-rank all-in-one path: nothing inside a time step reads pNHS (the projection takes its gradient from the solver's real
+  // buffer, the next solve overwrites it), so the projection leaves its store out and the field is written when somebody can
+  // look (api.hip pnhs_materialize).  pnhs_deferred set => the solver's real buffer holds exactly the values an eager
+  // projection would have stored in pNHS, and pNHS itself is out of date.  Whoever overwrites that buffer outside
+  // fused_substep materialises first (or clears the flag where it writes a complete new pNHS itself).
+  bool pnhs_deferred = false;
+  bool pnhs_escaped = false;     // ocn_field_device_ptr(pNHS) was called: reads can no longer be seen, every projection stores
+  int knob_eager_pressure = 0;   // OCNHIP_EAGER_PRESSURE=1: every projection stores pNHS (callers who read it after every step)
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
 };
@@ -154,6 +162,8 @@ extern thread_local int g_ocn_capturing, g_ocn_capture_poison;   // a library ca
 inline Field& pred_u(ocn_model* m) { return m->pred_active ? m->us : m->u; }
 inline Field& pred_v(ocn_model* m) { return m->pred_active ? m->vs : m->v; }
 inline Field& pred_w(ocn_model* m) { return m->pred_active ? m->ws : m->w; }
+// the model's projections leave the pNHS store to pnhs_materialize (see pnhs_deferred)
+inline bool pnhs_lazy(const ocn_model* m) { return m->fast_path && !m->g->dist && !m->knob_eager_pressure && !m->pnhs_escaped; }
 
 Field* model_field(ocn_model* m, int id);
 
@@ -198,7 +208,8 @@ void launch_tracer3(ocn_model* m, double dt, double cn, double cm, int use_m, bo
 // levels [zlo, zhi) (-1: Nz), optionally followed by a second run [zlo2, zhi2) of the same length in the same launch
 void launch_fused_tend_step(ocn_model* m, double dt, double cn, double cm, int use_m, int zlo = 0, int zhi = -1, int zlo2 = 0, int zhi2 = 0);
 void launch_rhs_wrap(ocn_model* m, double dt, double* rhs);
-void launch_project(ocn_model* m, double dt, const double* phi);
+void launch_project(ocn_model* m, double dt, const double* phi, bool store_p = true);
+void launch_pressure_images(ocn_model* m, const double* phi);   // pNHS with all periodic images from the compact (Nx, Ny, Nz) phi
 void launch_tracer_steps(ocn_model* m, double dt, double cn, double cm, int use_m);
 int fused_exchange_ws(ocn_model* m);
 int fused_exchange_phi(ocn_model* m, const double* phi);

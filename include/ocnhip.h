@@ -24,6 +24,15 @@
  *     of a model (every time-stepping path writes the corrected velocities back into the same arrays).  The
  *     tendency sets G^n / G^- and, on the tiled kernels' paths, the tracers are double buffered and ROTATE:
  *     re-query their pointers after every ocn_time_step (tests/test_model_contracts.py asserts both halves).
+ *   - when pNHS is current: on a single-rank model of the all-in-one periodic path no time step reads pNHS, so its
+ *     projections leave the field alone and the library writes it (interior and every periodic image) from the solver's
+ *     buffer when somebody asks: ocn_field_download / get_interior / set_interior(OCN_F_PNHS), ocn_fill_halos with the
+ *     pNHS bit, ocn_pressure_correct_velocities, and before ocn_poisson_solve_host / ocn_pressure_correction reuse the
+ *     solver's buffers.  Through these calls the field always reads as if every projection had stored it; the price is
+ *     one more launch and a second read of the 8 B / cell buffer per request.  ocn_sync does NOT write it.  Asking for
+ *     ocn_field_device_ptr(m, OCN_F_PNHS) writes the field and, since the library cannot see reads through the alias,
+ *     makes every later projection of that model store it again (ocn_model_path says so); the pointer stays the same.
+ *     OCNHIP_EAGER_PRESSURE=1 at model creation stores it in every projection from the start.
  *   - a model that needs wider halos than its grid has (WENO5 / U5: 3) works on a private copy of the grid with the
  *     wider halo, as the reference's with_halo does (nonhydrostatic_model.jl:140-148); the caller's grid and other
  *     models on it are left alone.
