@@ -95,7 +95,16 @@ struct ocn_hfield {
   double* d = nullptr;
   size_t n = 0;
   bool owned = true;
+  // the layout of the parent array, known here only: rows of T[0], levels of T[0] T[1] elements (long: the kernels' stride type)
+  long sy() const { return T[0]; }
+  long sz() const { return (long)T[0] * T[1]; }
 };
+// a field's data for a kernel that only reads it; null for a field that is absent (a buoyancy without T or without S)
+static const double* hfield_ro(const ocn_hfield* f) { return f ? f->d : nullptr; }
+// the launch shapes over a grid's interior, blocks of 64 x 4 threads: one thread per column (hy_cols) or per cell (hy_cells)
+static dim3 hy_block() { return dim3(64, 4, 1); }
+static dim3 hy_cols(const ocn_hgrid* g) { return dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1); }
+static dim3 hy_cells(const ocn_hgrid* g) { return dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]); }
 
 struct ocn_sefs {
   ocn_hgrid* g;
@@ -137,6 +146,11 @@ static void regular_axis(double c1, double L, int N, int H, int topo, std::vecto
   if (TC > 1) C[TC - 1] = Cp;
 }
 
+static int dev_alloc(ocn_ctx* ctx, double** d, size_t bytes) {
+  if (hipMalloc((void**)d, bytes) == hipSuccess) return OCN_OK;
+  ocn_set_error(ctx, "allocation of %zu bytes failed", bytes);
+  return OCN_ENOMEM;
+}
 static int upload(ocn_ctx* ctx, const std::vector<double>& h, double** d) {
   OCN_HIP_CHECK(ctx, hipMalloc((void**)d, (h.size() ? h.size() : 1) * sizeof(double)));
   if (!h.empty()) OCN_HIP_CHECK(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -220,8 +234,8 @@ static void hfield_fill(ocn_hfield* f, bool zfill = true) {
   ocn_hgrid* g = f->g;
   hipStream_t s = g->ctx->stream;
   if (zfill && f->loc[2] != OCN_NOTHING && (g->H[2] > 0 || f->loc[2] == OCN_FACE))
-    ocn_launch(k_h_fill_z, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), dim3(64, 4, 1), s, f->d, f->loc[2] == OCN_FACE ? 1 : 0, g->N[0], g->N[1],
-               g->N[2], g->H[0], g->H[1], g->H[2], f->T[0], f->T[1]);
+    ocn_launch(k_h_fill_z, hy_cols(g), hy_block(), s, f->d, f->loc[2] == OCN_FACE ? 1 : 0, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2],
+               f->T[0], f->T[1]);
   auto bounded = [&](int d, int sides) {
     const int o = 1 - d;
     if (!sides || (g->H[d] == 0 && f->loc[d] == OCN_CENTER)) return;
@@ -264,7 +278,7 @@ static int hfield_exchange_y(ocn_hfield* f) {
   const bool per = g->topo[1] == OCN_PERIODIC;
   const int up = (r + 1 < R) ? r + 1 : (per ? 0 : -1), dn = (r > 0) ? r - 1 : (per ? R - 1 : -1);
   const int extra = (f->loc[1] == OCN_FACE && !per) ? 1 : 0;
-  const size_t row = (size_t)f->T[0] * f->T[2];
+  const size_t row = (size_t)f->sy() * f->T[2];
   const size_t nA = (size_t)H * row, nB = (size_t)(H + extra) * row;      // block sent upwards / downwards
   const size_t need = nA + nB;
   if (need > g->pack_n) {
@@ -1146,15 +1160,9 @@ static SeArgs se_args(const ocn_sefs* s, double dtau, int index) {
   return a;
 }
 
-static void se_shape(const ocn_hgrid* g, dim3& b, dim3& gr) {
-  b = dim3(64, 4, 1);
-  gr = dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);
-}
-
 // split_explicit_free_surface_substep! as the reference issues it
 static void sefs_substep_plain(ocn_sefs* s, double dtau, int index) {
-  dim3 b, gr;
-  se_shape(s->g, b, gr);
+  const dim3 b = hy_block(), gr = hy_cols(s->g);
   hipStream_t st = s->g->ctx->stream;
   const SeArgs a = se_args(s, dtau, index);
   hfield_fill(s->eta);
@@ -1172,8 +1180,7 @@ static bool sefs_fusable(const ocn_sefs* s) {
 }
 
 static void sefs_substep_fused(ocn_sefs* s, double dtau, int index) {
-  dim3 b, gr;
-  se_shape(s->g, b, gr);
+  const dim3 b = hy_block(), gr = hy_cols(s->g);
   hipStream_t st = s->g->ctx->stream;
   const SeArgs a = se_args(s, dtau, index);
   ocn_launch(k_se_uv_fused, gr, b, st, a);
@@ -1182,8 +1189,7 @@ static void sefs_substep_fused(ocn_sefs* s, double dtau, int index) {
 
 // substep `index` in one launch; flip: 0 reads the fields' own arrays and writes the second set, 1 the other way round
 static void sefs_substep_one(ocn_sefs* s, double dtau, int index, int flip) {
-  dim3 b, gr;
-  se_shape(s->g, b, gr);
+  const dim3 b = hy_block(), gr = hy_cols(s->g);
   SeArgs1 q;
   q.a = se_args(s, dtau, index);
   q.etaI = flip ? s->eta2 : s->eta->d; q.UI = flip ? s->U2 : s->U->d; q.VI = flip ? s->V2 : s->V->d;
@@ -1232,10 +1238,9 @@ static int hfield_new(ocn_hgrid* g, int lx, int ly, int lz, ocn_hfield** out) {
     f->S[d] = interior_len(loc[d], g->topo[d], g->N[d]);
     f->n *= (size_t)f->T[d];
   }
-  if (hipMalloc((void**)&f->d, f->n * sizeof(double)) != hipSuccess) {
+  if (int rc = dev_alloc(g->ctx, &f->d, f->n * sizeof(double))) {
     delete f;
-    ocn_set_error(g->ctx, "allocation of %zu bytes failed", f->n * sizeof(double));
-    return OCN_ENOMEM;
+    return rc;
   }
   OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), g->ctx->stream));
   g->refs += 1;
@@ -1245,9 +1250,9 @@ static int hfield_new(ocn_hgrid* g, int lx, int ly, int lz, ocn_hfield** out) {
 
 static void vsum(ocn_sefs* s, ocn_hfield* out, const ocn_hfield* a, const ocn_hfield* b, double cn, double cm) {
   const ocn_hgrid* g = s->g;
-  dim3 blk(64, 4, 1), gr((out->S[0] + 63) / 64, (out->S[1] + 3) / 4, 1);
-  ocn_launch(k_se_vsum, gr, blk, g->ctx->stream, out->d, (const double*)a->d, b ? (const double*)b->d : (const double*)nullptr, cn, cm,
-             (const double*)g->dzc, out->S[0], out->S[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)a->T[0], (long)a->T[0] * a->T[1], (long)out->T[0]);
+  const dim3 blk = hy_block(), gr((out->S[0] + 63) / 64, (out->S[1] + 3) / 4, 1);
+  ocn_launch(k_se_vsum, gr, blk, g->ctx->stream, out->d, (const double*)a->d, hfield_ro(b), cn, cm, (const double*)g->dzc, out->S[0], out->S[1],
+             g->N[2], g->H[0], g->H[1], g->H[2], a->sy(), a->sz(), out->sy());
 }
 
 
@@ -1368,39 +1373,32 @@ static HyGrid hy_grid(const ocn_hgrid* g) {
   q.Nx = g->N[0]; q.Ny = g->N[1]; q.Nz = g->N[2]; q.Hx = g->H[0]; q.Hy = g->H[1]; q.Hz = g->H[2];
   return q;
 }
-static void hy_cols(const ocn_hgrid* g, dim3& b, dim3& gr) {
-  b = dim3(64, 4, 1);
-  gr = dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);
-}
+// the tracers the buoyancy reads, null for one it does not have
+static ocn_hfield* hydro_T(const ocn_hydro* h) { return h->bT >= 0 ? h->c[h->bT] : nullptr; }
+static ocn_hfield* hydro_S(const ocn_hydro* h) { return h->bS >= 0 ? h->c[h->bS] : nullptr; }
+// gmp: G^- as the kernel takes it -- k_hy_ab2_store writes it (G^- <- G^n in the same pass), k_hy_ab2 only reads it
 static void hy_ab2_launch(ocn_hfield* f, const ocn_hfield* gn, ocn_hfield* gm, double dt, double chi, bool store) {
   const ocn_hgrid* g = f->g;
-  dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
-  if (store)
-    ocn_launch(k_hy_ab2_store, gr, b, g->ctx->stream, f->d, (const double*)gn->d, gm->d, dt, 1.5 + chi, 0.5 + chi, g->N[0], g->N[1], g->N[2], g->H[0],
-               g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
-  else
-    ocn_launch(k_hy_ab2, gr, b, g->ctx->stream, f->d, (const double*)gn->d, (const double*)gm->d, dt, 1.5 + chi, 0.5 + chi, g->N[0], g->N[1], g->N[2],
-               g->H[0], g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
+#define HY_AB2(KERN, gmp)                                                                                                                  \
+  ocn_launch(KERN, hy_cells(g), hy_block(), g->ctx->stream, f->d, (const double*)gn->d, gmp, dt, 1.5 + chi, 0.5 + chi, g->N[0], g->N[1], g->N[2],  \
+             g->H[0], g->H[1], g->H[2], f->sy(), f->sz())
+  if (store) HY_AB2(k_hy_ab2_store, gm->d);
+  else HY_AB2(k_hy_ab2, (const double*)gm->d);
+#undef HY_AB2
 }
 static void hy_store_launch(ocn_hfield* gm, const ocn_hfield* gn) {
   const ocn_hgrid* g = gm->g;
-  dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
-  ocn_launch(k_hy_store, gr, b, g->ctx->stream, gm->d, (const double*)gn->d, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)gm->T[0],
-             (long)gm->T[0] * gm->T[1]);
+  ocn_launch(k_hy_store, hy_cells(g), hy_block(), g->ctx->stream, gm->d, (const double*)gn->d, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2],
+             gm->sy(), gm->sz());
 }
 static void hy_w_launch(const ocn_hfield* u, const ocn_hfield* v, ocn_hfield* w) {
   const ocn_hgrid* g = w->g;
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  ocn_launch(k_hy_w, gr, b, g->ctx->stream, hy_grid(g), (const double*)u->d, (const double*)v->d, w->d, (long)u->T[0], (long)u->T[0] * u->T[1],
-             (long)v->T[0], (long)v->T[0] * v->T[1], (long)w->T[0], (long)w->T[0] * w->T[1]);
+  ocn_launch(k_hy_w, hy_cols(g), hy_block(), g->ctx->stream, hy_grid(g), (const double*)u->d, (const double*)v->d, w->d, u->sy(), u->sz(), v->sy(),
+             v->sz(), w->sy(), w->sz());
 }
 static void hy_pressure_launch(ocn_hfield* p, const HyBuoy& q, const ocn_hfield* T, const ocn_hfield* S) {
   const ocn_hgrid* g = p->g;
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  ocn_launch(k_hy_pressure, gr, b, g->ctx->stream, hy_grid(g), q, T ? (const double*)T->d : (const double*)nullptr,
-             S ? (const double*)S->d : (const double*)nullptr, p->d, (long)p->T[0], (long)p->T[0] * p->T[1]);
+  ocn_launch(k_hy_pressure, hy_cols(g), hy_block(), g->ctx->stream, hy_grid(g), q, hfield_ro(T), hfield_ro(S), p->d, p->sy(), p->sz());
 }
 static bool is_loc(const ocn_hfield* f, const ocn_hgrid* g, int lx, int ly, int lz) {
   return f && f->g == g && f->loc[0] == lx && f->loc[1] == ly && f->loc[2] == lz;
@@ -1470,11 +1468,9 @@ static int sefs_step_tail(ocn_sefs* s, double dt) {
 // offU / offV: first element of the rows of u's grid inside the free surface's 2-D arrays (a latitude band; 0 otherwise)
 static void sefs_correct_launch(ocn_sefs* s, ocn_hfield* u, ocn_hfield* v, long offU = 0, long offV = 0) {
   const ocn_hgrid* g = u->g;
-  dim3 blk(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);
-  ocn_launch(k_se_correct, gr, blk, g->ctx->stream, u->d, v->d, (const double*)s->U->d + offU, (const double*)s->V->d + offV,
+  ocn_launch(k_se_correct, hy_cols(g), hy_block(), g->ctx->stream, u->d, v->d, (const double*)s->U->d + offU, (const double*)s->V->d + offV,
              (const double*)s->Ubar->d + offU, (const double*)s->Vbar->d + offV, (const double*)s->Hfc->d + offU, (const double*)s->Hcf->d + offV, g->N[0],
-             g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],
-             (long)s->U->T[0], (long)s->V->T[0]);
+             g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], u->sy(), u->sz(), v->sy(), v->sz(), s->U->sy(), s->V->sy());
 }
 
 // every band's rows of the listed (Face, Center) / (Center, Face) arrays of the replicated free surface to every other rank: rows are
@@ -1504,26 +1500,22 @@ static int hydro_allgather_rows(ocn_hydro* h) {
 // calculate_diffusivities! of the ConvectiveAdjustmentVerticalDiffusivity, halos included (hyconvect.h)
 static void hydro_cv_diffusivities(ocn_hydro* h) {
   const ocn_hgrid* g = h->lg;
-  ocn_hfield *K = h->cv.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  ocn_hfield* K = h->cv.kap;
   const bool yb = g->topo[1] != OCN_PERIODIC;
-  ocn_launch(k_hy_cv_diff, dim3((K->T[0] + 63) / 64, (K->T[1] + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, hy_grid(g), h->buoy, h->cv.kc, h->cv.nuc,
-             h->cv.kb, h->cv.nub, T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, K->d, h->cv.nu->d,
-             K->T[0], K->T[1], (int)(g->topo[0] != OCN_PERIODIC), (int)(yb && g->wall_lo), (int)(yb && g->wall_hi), (long)K->T[0],
-             (long)K->T[0] * K->T[1]);
+  ocn_launch(k_hy_cv_diff, dim3((K->T[0] + 63) / 64, (K->T[1] + 3) / 4, 1), hy_block(), g->ctx->stream, hy_grid(g), h->buoy, h->cv.kc, h->cv.nuc,
+             h->cv.kb, h->cv.nub, hfield_ro(hydro_T(h)), hfield_ro(hydro_S(h)), K->d, h->cv.nu->d, K->T[0], K->T[1],
+             (int)(g->topo[0] != OCN_PERIODIC), (int)(yb && g->wall_lo), (int)(yb && g->wall_hi), K->sy(), K->sz());
 }
 // calculate_diffusivities! of the RiBasedVerticalDiffusivity (hyribased.h): the interior columns, then the fills of a Center field
 // in x / y (with the band exchange) and, for a Center location, the no-flux fill in z
 static void hydro_rb_diffusivities(ocn_hydro* h) {
   const ocn_hgrid* g = h->lg;
-  ocn_hfield *K = h->rb.kap, *N = h->rb.nu, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
+  ocn_hfield *K = h->rb.kap, *N = h->rb.nu;
   const ocn_hfield *u = h->u, *v = h->v, *c = h->c.empty() ? nullptr : h->c[0];
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  const long sy = c ? c->T[0] : 0, sz = c ? (long)c->T[0] * c->T[1] : 0;
+  const long sy = c ? c->sy() : 0, sz = c ? c->sz() : 0;
 #define HY_RI(TP)                                                                                                                          \
-  ocn_launch(k_hy_ri_diff<TP>, gr, b, g->ctx->stream, hy_grid(g), h->buoy, h->rb.rp, (const double*)u->d, (const double*)v->d,               \
-             T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, K->d, N->d, (long)u->T[0],    \
-             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], sy, sz, (long)K->T[0], (long)K->T[0] * K->T[1])
+  ocn_launch(k_hy_ri_diff<TP>, hy_cols(g), hy_block(), g->ctx->stream, hy_grid(g), h->buoy, h->rb.rp, (const double*)u->d, (const double*)v->d, \
+             hfield_ro(hydro_T(h)), hfield_ro(hydro_S(h)), K->d, N->d, u->sy(), u->sz(), v->sy(), v->sz(), sy, sz, K->sy(), K->sz())
   if (h->rb.taper == 0) HY_RI(0);
   else if (h->rb.taper == 1) HY_RI(1);
   else HY_RI(2);
@@ -1546,11 +1538,9 @@ static bool hydro_cv_center(const ocn_hydro* h) { const ocn_hydro::Cavd* v = hyd
 static void hydro_iso_diffusivities(ocn_hydro* h) {
   const ocn_hgrid* g = h->lg;
   ocn_hydro::Iso& s = h->iso;
-  const ocn_hfield *K = s.er33, *T = h->c[h->bT], *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
-  const long syk = K->T[0], szk = (long)K->T[0] * K->T[1];
-  ocn_launch(k_hy_iso_slopes, dim3((g->N[0] + 1 + 63) / 64, (g->N[1] + 1 + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, hy_metric(g), h->buoy, s.p,
-             s.dzf_top, (const double*)T->d, S ? (const double*)S->d : (const double*)nullptr, s.w[0], s.w[1], s.w[2], s.w[3], s.w[4], K->d,
-             (long)T->T[0], (long)T->T[0] * T->T[1], syk, szk);
+  const ocn_hfield *K = s.er33, *T = h->c[h->bT];
+  ocn_launch(k_hy_iso_slopes, dim3((g->N[0] + 1 + 63) / 64, (g->N[1] + 1 + 3) / 4, 1), hy_block(), g->ctx->stream, hy_metric(g), h->buoy, s.p, s.dzf_top,
+             (const double*)T->d, hfield_ro(hydro_S(h)), s.w[0], s.w[1], s.w[2], s.w[3], s.w[4], K->d, T->sy(), T->sz(), K->sy(), K->sz());
   hfield_fill(s.er33, false);
   const ocn_hydro::Cavd* v = hydro_vk(h);
   const double* vk = v && v->disc == 0 && v->nzc ? (const double*)v->kap->d : (const double*)nullptr;
@@ -1558,68 +1548,61 @@ static void hydro_iso_diffusivities(ocn_hydro* h) {
     double ks = 0.0;
     for (size_t q = 0; q < s.kzi.size(); ++q)
       if (s.kzi[q] == (int)e) ks = s.ks[q];
-    ocn_launch(k_hy_iso_kz, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]), dim3(64, 4, 1), g->ctx->stream, g->N[0], g->N[1], g->N[2],
-               g->H[0], g->H[1], g->H[2], ks, (const double*)K->d, vk, s.kz[e], syk, szk);
+    ocn_launch(k_hy_iso_kz, hy_cells(g), hy_block(), g->ctx->stream, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], ks, (const double*)K->d, vk,
+               s.kz[e], K->sy(), K->sz());
   }
 }
 static HyCvSolve hydro_cv_solve(const ocn_hydro* h, int q) {      // q: entry of h->kap (0 u / v, 1 + n tracer n)
   if (h->iso.on && q > 0) {
     const ocn_hfield* K = h->iso.er33;
-    return HyCvSolve{h->iso.kz[h->iso.kzi[q - 1]], (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->iso.t};
+    return HyCvSolve{h->iso.kz[h->iso.kzi[q - 1]], K->sy(), K->sz(), (size_t)q < h->kap.size() ? h->kap[q] : 0.0, h->iso.t};
   }
   const ocn_hydro::Cavd* v = hydro_vk(h);
   const ocn_hfield* K = q == 0 ? v->nu : (h->ck.on && q - 1 == h->catke.eidx) ? h->catke.Ke : v->kap;
-  return HyCvSolve{K->d, (long)K->T[0], (long)K->T[0] * K->T[1], (size_t)q < h->kap.size() ? h->kap[q] : 0.0, v->t};
+  return HyCvSolve{K->d, K->sy(), K->sz(), (size_t)q < h->kap.size() ? h->kap[q] : 0.0, v->t};
 }
 // the tracer e of a CATKEVerticalDiffusivity that stands alone: its solve carries L^e on the diagonal (q: entry of h->kap)
 static bool hydro_catke_lin(const ocn_hydro* h, int q) { return h->ck.on && h->catke.lin && q - 1 == h->catke.eidx; }
 static HyCvLin hydro_catke_lin_arg(const ocn_hydro* h) {
   const ocn_hfield* L = h->catke.Le;
-  return HyCvLin{L->d, (long)L->T[0], (long)L->T[0] * L->T[1]};
+  return HyCvLin{L->d, L->sy(), L->sz()};
 }
 // calculate_diffusivities! of the CATKEVerticalDiffusivity (hycatke.h): one launch over the interior columns, then the x / y fills of
 // K^u (with the band exchange), the field whose halos the solves and the w-shear term of u and v read
 static void hydro_catke_diffusivities(ocn_hydro* h) {
   const ocn_hgrid* g = h->lg;
   const ocn_hydro::Catke& k = h->catke;
-  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
-  const ocn_hfield *u = h->u, *v = h->v, *e = h->c[k.eidx];
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  ocn_launch(k_hy_catke_diff, gr, b, g->ctx->stream, hy_grid(g), h->buoy, k.p, (const double*)k.dw, k.has_qb ? (const double*)k.Qb : (const double*)nullptr,
-             (const double*)u->d, (const double*)v->d, T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr,
-             (const double*)e->d, Ku->d, Kc->d, k.Ke->d, k.Le->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],
-             (long)e->T[0], (long)e->T[0] * e->T[1], (long)Ku->T[0], (long)Ku->T[0] * Ku->T[1], (long)k.Le->T[0], (long)k.Le->T[0] * k.Le->T[1]);
+  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *u = h->u, *v = h->v, *e = h->c[k.eidx];
+  ocn_launch(k_hy_catke_diff, hy_cols(g), hy_block(), g->ctx->stream, hy_grid(g), h->buoy, k.p, (const double*)k.dw,
+             k.has_qb ? (const double*)k.Qb : (const double*)nullptr, (const double*)u->d, (const double*)v->d, hfield_ro(hydro_T(h)),
+             hfield_ro(hydro_S(h)), (const double*)e->d, Ku->d, Kc->d, k.Ke->d, k.Le->d, u->sy(), u->sz(), v->sy(), v->sz(), e->sy(), e->sz(), Ku->sy(),
+             Ku->sz(), k.Le->sy(), k.Le->sz());
   hfield_fill(h->ck.nu, false);
 }
 // the source terms of the TKE tendency (shear production, buoyancy flux), after the tracer pass and before the flux conditions
 static void hydro_catke_sources(ocn_hydro* h) {
   if (!h->ck.on) return;
   const ocn_hgrid* g = h->lg;
-  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *T = h->bT >= 0 ? h->c[h->bT] : nullptr, *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
-  const ocn_hfield *u = h->u, *v = h->v, *e = h->c[h->catke.eidx];
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  ocn_launch(k_hy_catke_src, gr, b, g->ctx->stream, hy_grid(g), h->buoy, (const double*)u->d, (const double*)v->d,
-             T ? (const double*)T->d : (const double*)nullptr, S ? (const double*)S->d : (const double*)nullptr, (const double*)Ku->d,
-             (const double*)Kc->d, h->gn[2 + h->catke.eidx]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],
-             (long)e->T[0], (long)e->T[0] * e->T[1], (long)Ku->T[0], (long)Ku->T[0] * Ku->T[1]);
+  const ocn_hfield *Ku = h->ck.nu, *Kc = h->ck.kap, *u = h->u, *v = h->v, *e = h->c[h->catke.eidx];
+  ocn_launch(k_hy_catke_src, hy_cols(g), hy_block(), g->ctx->stream, hy_grid(g), h->buoy, (const double*)u->d, (const double*)v->d, hfield_ro(hydro_T(h)),
+             hfield_ro(hydro_S(h)), (const double*)Ku->d, (const double*)Kc->d, h->gn[2 + h->catke.eidx]->d, u->sy(), u->sz(), v->sy(), v->sz(), e->sy(),
+             e->sz(), Ku->sy(), Ku->sz());
 }
 // loc: 0 a tracer, 1 u, 2 v (+ 3 for Center-location coefficients)
 static void hydro_cv_implicit_launch(ocn_hydro* h, ocn_hfield* f, int loc, int q, double dt) {
   const ocn_hgrid* g = h->lg;
-  dim3 b, gr;
-  hy_cols(g, b, gr);
   const HyCvSolve s = hydro_cv_solve(h, q);
-  const long sy = f->T[0], sz = (long)f->T[0] * f->T[1];
   loc += hydro_cv_center(h) ? 3 : 0;
-  if (loc == 0 && hydro_catke_lin(h, q)) ocn_launch(k_hy_cv_implicit_lin, gr, b, g->ctx->stream, f->d, s, hydro_catke_lin_arg(h), hy_grid(g), dt, sy, sz);
-  else if (loc == 0) ocn_launch(k_hy_cv_implicit<0>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else if (loc == 1) ocn_launch(k_hy_cv_implicit<1>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else if (loc == 2) ocn_launch(k_hy_cv_implicit<2>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else if (loc == 3) ocn_launch(k_hy_cv_implicit<3>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else if (loc == 4) ocn_launch(k_hy_cv_implicit<4>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
-  else ocn_launch(k_hy_cv_implicit<5>, gr, b, g->ctx->stream, f->d, s, hy_grid(g), dt, sy, sz);
+#define HY_CV_IMPLICIT(LOC) ocn_launch(k_hy_cv_implicit<LOC>, hy_cols(g), hy_block(), g->ctx->stream, f->d, s, hy_grid(g), dt, f->sy(), f->sz())
+  if (loc == 0 && hydro_catke_lin(h, q))
+    ocn_launch(k_hy_cv_implicit_lin, hy_cols(g), hy_block(), g->ctx->stream, f->d, s, hydro_catke_lin_arg(h), hy_grid(g), dt, f->sy(), f->sz());
+  else if (loc == 0) HY_CV_IMPLICIT(0);
+  else if (loc == 1) HY_CV_IMPLICIT(1);
+  else if (loc == 2) HY_CV_IMPLICIT(2);
+  else if (loc == 3) HY_CV_IMPLICIT(3);
+  else if (loc == 4) HY_CV_IMPLICIT(4);
+  else HY_CV_IMPLICIT(5);
+#undef HY_CV_IMPLICIT
 }
 // update_state!: fills of the prognostic fields, w from continuity, the hydrostatic pressure, fills of w and pHY'
 static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
@@ -1632,7 +1615,7 @@ static void hydro_update_state(ocn_hydro* h, bool pressure_done) {
   if (h->rb.on) hydro_rb_diffusivities(h);
   if (h->ck.on) hydro_catke_diffusivities(h);
   if (h->iso.on) hydro_iso_diffusivities(h);
-  if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, h->bT >= 0 ? h->c[h->bT] : nullptr, h->bS >= 0 ? h->c[h->bS] : nullptr);
+  if (!pressure_done) hy_pressure_launch(h->pHY, h->buoy, hydro_T(h), hydro_S(h));
   hfield_fill(h->w);
   hfield_fill(h->pHY);
 }
@@ -1646,7 +1629,7 @@ static HyMetric hy_metric(const ocn_hgrid* g) {
 }
 static void hydro_tendencies(ocn_hydro* h) {
   const ocn_hgrid* g = h->lg;
-  dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
+  const dim3 b = hy_block(), gr = hy_cols(g);          // one thread per column
   const ocn_hfield *u = h->u, *v = h->v, *p = h->pHY;
   HyPhys ph = h->phys;
   ph.frow = h->frow;
@@ -1654,33 +1637,37 @@ static void hydro_tendencies(ocn_hydro* h) {
   ph.yb = g->topo[1] != OCN_PERIODIC;
   ph.jrow0 = g->j0;
   ph.gNy = g->gNy;
-#define HY_GUV(VS)                                                                                                                         \
-  ocn_launch(k_hy_Guv<VS>, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d,         \
-             (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (long)u->T[0],                     \
-             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1])
-#define HY_GUV_FLUX(ADVV)                                                                                                                  \
-  ocn_launch(k_hy_Guv_flux<ADVV>, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d, \
-             (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (long)u->T[0],                     \
-             (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1])
+  // what every kernel here ends with, and what the momentum kernels start with (k_hy_Guv_flux_sz takes its table between the two)
+#define HY_UVP_STRIDES u->sy(), u->sz(), v->sy(), v->sz(), p->sy(), p->sz()
+#define HY_GUV_FIELDS                                                                                                                      \
+  hy_metric(g), ph, (const double*)u->d, (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d
+#define HY_GUV(KERN) ocn_launch(KERN, gr, b, g->ctx->stream, HY_GUV_FIELDS, HY_UVP_STRIDES)
   switch (h->mflux) {
-    case 1: HY_GUV_FLUX(ADV_C2); break;
-    case 2: HY_GUV_FLUX(ADV_C4); break;
-    case 3: HY_GUV_FLUX(ADV_U1); break;
-    case 4: HY_GUV_FLUX(ADV_U3); break;
-    case 5: HY_GUV_FLUX(ADV_U5); break;
+    case 1: HY_GUV(k_hy_Guv_flux<ADV_C2>); break;
+    case 2: HY_GUV(k_hy_Guv_flux<ADV_C4>); break;
+    case 3: HY_GUV(k_hy_Guv_flux<ADV_U1>); break;
+    case 4: HY_GUV(k_hy_Guv_flux<ADV_U3>); break;
+    case 5: HY_GUV(k_hy_Guv_flux<ADV_U5>); break;
     case 6:
       if (h->sz_momentum && h->sz_tab && g->N[2] > 3)      // up to three levels every z face lies inside the boundary buffer: nothing reads the table
-        ocn_launch(k_hy_Guv_flux_sz, dim3((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1), b, g->ctx->stream, hy_metric(g), ph, (const double*)u->d,
-                   (const double*)v->d, (const double*)h->w->d, (const double*)p->d, h->gn[0]->d, h->gn[1]->d, (const double*)h->sz_tab,
-                   (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
-      else HY_GUV_FLUX(ADV_WENO_Z);
+        ocn_launch(k_hy_Guv_flux_sz, gr, b, g->ctx->stream, HY_GUV_FIELDS, (const double*)h->sz_tab, HY_UVP_STRIDES);
+      else HY_GUV(k_hy_Guv_flux<ADV_WENO_Z>);
       break;
     default:
-      if (ph.madv == 4) HY_GUV(true);
-      else HY_GUV(false);
+      if (ph.madv == 4) HY_GUV(k_hy_Guv<true>);
+      else HY_GUV(k_hy_Guv<false>);
   }
-#undef HY_GUV_FLUX
 #undef HY_GUV
+#undef HY_GUV_FIELDS
+  // the tracers, two per launch (NT = 2) and a last odd one alone (NT = 1)
+#define HY_GC_FIELDS hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1, G0, G1
+#define HY_GC_SZ(NT)                                                                                                                       \
+  ocn_launch(k_hy_Gc_sz<NT>, gr, b, g->ctx->stream, HY_GC_FIELDS, (const double*)h->sz_tab, xb, yb, g->j0, g->gNy, HY_UVP_STRIDES)
+#define HY_GC_HI(ADVV, NT) ocn_launch(k_hy_Gc_hi<ADVV, NT>, gr, b, g->ctx->stream, HY_GC_FIELDS, xb, yb, g->j0, g->gNy, HY_UVP_STRIDES)
+#define HY_GC(NT) ocn_launch(k_hy_Gc<NT>, gr, b, g->ctx->stream, HY_GC_FIELDS, h->phys.tadv, HY_UVP_STRIDES)
+#define HY_GC_HI2(ADVV)                                                                                                                    \
+  if (two) HY_GC_HI(ADVV, 2);                                                                                                              \
+  else HY_GC_HI(ADVV, 1);
   for (size_t q = 0; q < h->c.size(); q += 2) {
     const bool two = q + 1 < h->c.size();
     const double *c0 = h->c[q]->d, *c1 = two ? h->c[q + 1]->d : nullptr;
@@ -1689,39 +1676,21 @@ static void hydro_tendencies(ocn_hydro* h) {
     if (tadv >= 2) {
       // CenteredFourthOrder / UpwindBiasedFifthOrder / WENO5
       const int xb = g->topo[0] != OCN_PERIODIC, yb = g->topo[1] != OCN_PERIODIC;
-      const dim3 grh((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);          // one thread per column
       if (tadv == 4 && h->sz_tracers && h->sz_tab && g->N[2] > 3) {      // Nz <= 3: no z face outside the buffer, the uniform kernel is the scheme
-        if (two)
-          ocn_launch(k_hy_Gc_sz<2>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1,
-                     G0, G1, (const double*)h->sz_tab, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
-                     (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
-        else
-          ocn_launch(k_hy_Gc_sz<1>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1,
-                     G0, G1, (const double*)h->sz_tab, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
-                     (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
-        continue;
-      }
-#define HY_GC_HI(ADVV)                                                                                                                     \
-  if (two)                                                                                                                                 \
-    ocn_launch(k_hy_Gc_hi<ADVV, 2>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d,  \
-               c0, c1, G0, G1, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],        \
-               (long)p->T[0], (long)p->T[0] * p->T[1]);                                                                                    \
-  else                                                                                                                                     \
-    ocn_launch(k_hy_Gc_hi<ADVV, 1>, grh, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d,  \
-               c0, c1, G0, G1, xb, yb, g->j0, g->gNy, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1],        \
-               (long)p->T[0], (long)p->T[0] * p->T[1]);
-      if (tadv == 2) { HY_GC_HI(ADV_C4) } else if (tadv == 3) { HY_GC_HI(ADV_U5) } else { HY_GC_HI(ADV_WENO_Z) }
-#undef HY_GC_HI
+        if (two) HY_GC_SZ(2);
+        else HY_GC_SZ(1);
+      } else if (tadv == 2) { HY_GC_HI2(ADV_C4) } else if (tadv == 3) { HY_GC_HI2(ADV_U5) } else { HY_GC_HI2(ADV_WENO_Z) }
       continue;
     }
-    const dim3 grc((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);          // one thread per column
-    if (two)
-      ocn_launch(k_hy_Gc<2>, grc, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1, G0, G1,
-                 h->phys.tadv, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
-    else
-      ocn_launch(k_hy_Gc<1>, grc, b, g->ctx->stream, hy_metric(g), (const double*)u->d, (const double*)v->d, (const double*)h->w->d, c0, c1, G0, G1,
-                 h->phys.tadv, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], (long)p->T[0], (long)p->T[0] * p->T[1]);
+    if (two) HY_GC(2);
+    else HY_GC(1);
   }
+#undef HY_GC_HI2
+#undef HY_GC
+#undef HY_GC_HI
+#undef HY_GC_SZ
+#undef HY_GC_FIELDS
+#undef HY_UVP_STRIDES
 }
 
 // the explicit horizontal closures: G <- G - (Laplacian + biharmonic term) after the advection kernels (hyclosure.h); nothing is
@@ -1753,14 +1722,13 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
   const int vzc = cv.on && cv.disc == 1 && cv.nzc ? 1 + zc3 : 0;
   if (h->kap2.empty() && !vzu && !vzc) return;
   const ocn_hgrid* g = h->lg;
-  const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
+  const dim3 b = hy_block(), gr = hy_cells(g);
   const HyClo m{g->topo[0] != OCN_PERIODIC, g->topo[1] != OCN_PERIODIC, g->j0, g->gNy};
   const ocn_hfield *u = h->u, *v = h->v;
   const double nu = h->kap2.empty() ? 0.0 : h->kap2[0], nu4 = h->kap4.empty() ? 0.0 : h->kap4[0];
   HyCvTerm zu{}, zc{};
   if (vzu || vzc) {
-    zu = HyCvTerm{cv.nu->d, h->w->d, (long)cv.nu->T[0], (long)cv.nu->T[0] * cv.nu->T[1], (long)h->w->T[0], (long)h->w->T[0] * h->w->T[1],
-                  cv.order[0], cv.order[1], cv.order[2]};
+    zu = HyCvTerm{cv.nu->d, h->w->d, cv.nu->sy(), cv.nu->sz(), h->w->sy(), h->w->sz(), cv.order[0], cv.order[1], cv.order[2]};
     zc = zu;
     zc.K = cv.kap->d;
     zc.o0 = cv.order_c[0]; zc.o1 = cv.order_c[1]; zc.o2 = cv.order_c[2];
@@ -1768,79 +1736,67 @@ static void hydro_horizontal_closures(ocn_hydro* h) {
   // a viscosity table or a divergence formulation: the instances of hyclosure_var.h; every other launch below is as it was
   const bool uvar = hydro_coef_table(h, 0, 0) || hydro_coef_table(h, 1, 0) || (h->hform[0] && hydro_coef_on(h, 0, 0)) ||
                     (h->hform[1] && hydro_coef_on(h, 1, 0));
-#define HY_CLO_UV(LAP, BIH)                                                                                                                \
-  ocn_launch(k_hy_clo_uv<LAP, BIH>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d, h->gn[0]->d, \
-             h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], HyCvTerm{})
-#define HY_CLO_UVZ(LAP, BIH, VZ)                                                                                                           \
-  ocn_launch(k_hy_clo_uv<LAP, BIH, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d,          \
-             h->gn[0]->d, h->gn[1]->d, (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], zu)
+  // ZT: the vertical term the instance reads (zu), HyCvTerm{} for one without; `...`: LAP, BIH and, with a vertical term, VZ
+#define HY_CLO_UV(ZT, ...)                                                                                                                 \
+  ocn_launch(k_hy_clo_uv<__VA_ARGS__>, gr, b, g->ctx->stream, hy_metric(g), m, nu, nu4, (const double*)u->d, (const double*)v->d, h->gn[0]->d, \
+             h->gn[1]->d, u->sy(), u->sz(), v->sy(), v->sz(), ZT)
 #define HY_CLO_UV3(VZ)                                                                                                                     \
-  if (nu != 0.0 && nu4 != 0.0) HY_CLO_UVZ(true, true, VZ);                                                                                 \
-  else if (nu != 0.0) HY_CLO_UVZ(true, false, VZ);                                                                                         \
-  else if (nu4 != 0.0) HY_CLO_UVZ(false, true, VZ);                                                                                        \
-  else HY_CLO_UVZ(false, false, VZ);
+  if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(zu, true, true, VZ);                                                                              \
+  else if (nu != 0.0) HY_CLO_UV(zu, true, false, VZ);                                                                                      \
+  else if (nu4 != 0.0) HY_CLO_UV(zu, false, true, VZ);                                                                                     \
+  else HY_CLO_UV(zu, false, false, VZ);
   if (uvar) {
     const HyCloUVArgs a{hy_metric(g), m, hydro_coef(h, 0, 0), hydro_coef(h, 1, 0), g->N[1] + 2 * g->H[1] + 1, u->d, v->d, h->gn[0]->d, h->gn[1]->d,
-                        (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0], (long)v->T[0] * v->T[1], zu};
+                        u->sy(), u->sz(), v->sy(), v->sz(), zu};
     hy_clo_uv_var(vzu, hydro_coef_on(h, 0, 0), hydro_coef_on(h, 1, 0), h->hform[0] != 0, h->hform[1] != 0, gr, b, g->ctx->stream, a);
   }
   else if (vzu == 1) { HY_CLO_UV3(1) }
   else if (vzu == 2) { HY_CLO_UV3(2) }
   else if (vzu == 3) { HY_CLO_UV3(3) }
   else if (vzu == 4) { HY_CLO_UV3(4) }
-  else if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(true, true);
-  else if (nu != 0.0) HY_CLO_UV(true, false);
-  else if (nu4 != 0.0) HY_CLO_UV(false, true);
+  else if (nu != 0.0 && nu4 != 0.0) HY_CLO_UV(HyCvTerm{}, true, true);
+  else if (nu != 0.0) HY_CLO_UV(HyCvTerm{}, true, false);
+  else if (nu4 != 0.0) HY_CLO_UV(HyCvTerm{}, false, true);
 #undef HY_CLO_UV3
-#undef HY_CLO_UVZ
 #undef HY_CLO_UV
+  // the tracers, two per launch (NT = 2) and a last odd one alone (NT = 1); `...` of HY_CLO_C: LAP, BIH, NT and, with a vertical term, VZ
+#define HY_CLO_C(ZT, ...)                                                                                                                  \
+  ocn_launch(k_hy_clo_c<__VA_ARGS__>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, c->sy(), c->sz(), ZT)
+#define HY_CLO_CZV(LAP, BIH, VZ)                                                                                                           \
+  if (two) HY_CLO_C(zc, LAP, BIH, 2, VZ);                                                                                                  \
+  else HY_CLO_C(zc, LAP, BIH, 1, VZ);
+#define HY_CLO_CZ(LAP, BIH)                                                                                                                \
+  if (vzc == 3) { HY_CLO_CZV(LAP, BIH, 3) } else { HY_CLO_CZV(LAP, BIH, 1) }
+#define HY_CLO_C0(LAP, BIH)                                                                                                                \
+  if (two) HY_CLO_C(HyCvTerm{}, LAP, BIH, 2);                                                                                              \
+  else HY_CLO_C(HyCvTerm{}, LAP, BIH, 1);
   for (size_t q = 0; q < h->c.size(); q += 2) {
     const bool two = q + 1 < h->c.size();
     const bool hz = !h->kap2.empty();
     const double k0 = hz ? h->kap2[1 + q] : 0.0, k1 = hz && two ? h->kap2[2 + q] : 0.0, k40 = hz ? h->kap4[1 + q] : 0.0,
                  k41 = hz && two ? h->kap4[2 + q] : 0.0;
     const bool lap = k0 != 0.0 || k1 != 0.0, bih = k40 != 0.0 || k41 != 0.0;
+    const ocn_hfield* c = h->c[q];
+    const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
+    double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
     if (hydro_coef_table(h, 0, 1 + q) || hydro_coef_table(h, 1, 1 + q) || (two && (hydro_coef_table(h, 0, 2 + q) || hydro_coef_table(h, 1, 2 + q)))) {
-      const ocn_hfield* c = h->c[q];
       const HyCloCArgs a{hy_metric(g), m, HyCoef2{{hydro_coef(h, 0, 1 + q), two ? hydro_coef(h, 0, 2 + q) : HyCoef{}}},
-                         HyCoef2{{hydro_coef(h, 1, 1 + q), two ? hydro_coef(h, 1, 2 + q) : HyCoef{}}}, g->N[1] + 2 * g->H[1] + 1, c->d, two ? h->c[q + 1]->d : nullptr,
-                         h->gn[2 + q]->d, two ? h->gn[3 + q]->d : nullptr, (long)c->T[0], (long)c->T[0] * c->T[1], zc};
+                         HyCoef2{{hydro_coef(h, 1, 1 + q), two ? hydro_coef(h, 1, 2 + q) : HyCoef{}}}, g->N[1] + 2 * g->H[1] + 1, c0, c1, G0, G1,
+                         c->sy(), c->sz(), zc};
       hy_clo_c_var(vzc, two, hydro_coef_on(h, 0, 1 + q) || (two && hydro_coef_on(h, 0, 2 + q)),
                    hydro_coef_on(h, 1, 1 + q) || (two && hydro_coef_on(h, 1, 2 + q)), gr, b, g->ctx->stream, a);
       continue;
     }
     if (vzc) {
-      const ocn_hfield* c = h->c[q];
-      const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
-      double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
-#define HY_CLO_CZV(LAP, BIH, VZ)                                                                                                           \
-  if (two)                                                                                                                                 \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 2, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],         \
-               (long)c->T[0] * c->T[1], zc);                                                                                               \
-  else                                                                                                                                     \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 1, VZ>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],         \
-               (long)c->T[0] * c->T[1], zc);
-#define HY_CLO_CZ(LAP, BIH)                                                                                                                \
-  if (vzc == 3) { HY_CLO_CZV(LAP, BIH, 3) } else { HY_CLO_CZV(LAP, BIH, 1) }
       if (lap && bih) { HY_CLO_CZ(true, true) } else if (lap) { HY_CLO_CZ(true, false) } else if (bih) { HY_CLO_CZ(false, true) } else { HY_CLO_CZ(false, false) }
-#undef HY_CLO_CZ
-#undef HY_CLO_CZV
       continue;
     }
-    if (!lap && !bih) continue;
-    const ocn_hfield* c = h->c[q];
-    const double *c0 = c->d, *c1 = two ? h->c[q + 1]->d : nullptr;
-    double *G0 = h->gn[2 + q]->d, *G1 = two ? h->gn[3 + q]->d : nullptr;
-#define HY_CLO_C(LAP, BIH)                                                                                                                 \
-  if (two)                                                                                                                                 \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 2>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
-               (long)c->T[0] * c->T[1], HyCvTerm{});                                                                                       \
-  else                                                                                                                                     \
-    ocn_launch(k_hy_clo_c<LAP, BIH, 1>, gr, b, g->ctx->stream, hy_metric(g), m, k0, k1, k40, k41, c0, c1, G0, G1, (long)c->T[0],             \
-               (long)c->T[0] * c->T[1], HyCvTerm{});
-    if (lap && bih) { HY_CLO_C(true, true) } else if (lap) { HY_CLO_C(true, false) } else { HY_CLO_C(false, true) }
-#undef HY_CLO_C
+    if (lap && bih) { HY_CLO_C0(true, true) } else if (lap) { HY_CLO_C0(true, false) } else if (bih) { HY_CLO_C0(false, true) }
   }
+#undef HY_CLO_C0
+#undef HY_CLO_CZ
+#undef HY_CLO_CZV
+#undef HY_CLO_C
 }
 
 // the IsopycnalSkewSymmetricDiffusivity's explicit fluxes (hyisopycnal.h): G_c <- G_c - div q for every tracer, one launch per
@@ -1851,7 +1807,6 @@ static void hydro_iso_fluxes(ocn_hydro* h) {
   if (!s.on) return;
   const ocn_hgrid* g = h->lg;
   const ocn_hfield* K = s.er33;
-  const dim3 b(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, g->N[2]);
   for (size_t q0 = 0; q0 < h->c.size(); q0 += HY_ISO_MAXT) {
     HyIsoTracers tr;
     tr.n = 0;
@@ -1864,8 +1819,8 @@ static void hydro_iso_fluxes(ocn_hydro* h) {
     }
     if (!tr.n) continue;
     const ocn_hfield* c = h->c[q0];
-    ocn_launch(k_hy_iso_flux, gr, b, g->ctx->stream, hy_metric(g), tr, (const double*)s.w[0], (const double*)s.w[1], (const double*)s.w[2],
-               (const double*)s.w[3], (const double*)s.w[4], (long)c->T[0], (long)c->T[0] * c->T[1], (long)K->T[0], (long)K->T[0] * K->T[1]);
+    ocn_launch(k_hy_iso_flux, hy_cells(g), hy_block(), g->ctx->stream, hy_metric(g), tr, (const double*)s.w[0], (const double*)s.w[1],
+               (const double*)s.w[2], (const double*)s.w[3], (const double*)s.w[4], c->sy(), c->sz(), K->sy(), K->sz());
   }
 }
 
@@ -1883,7 +1838,7 @@ static void hydro_flux_bcs(ocn_hydro* h) {
       if (!t.n) return;
       if (dir == 0) ocn_launch(k_hy_flux_x, dim3((Ny + 63) / 64, Nz, 1), dim3(64, 1, 1), g->ctx->stream, m, t);
       else if (dir == 1) ocn_launch(k_hy_flux_y, dim3((Nx + 63) / 64, Nz, 1), dim3(64, 1, 1), g->ctx->stream, m, t);
-      else ocn_launch(k_hy_flux_z, dim3((Nx + 63) / 64, (Ny + 3) / 4, 1), dim3(64, 4, 1), g->ctx->stream, m, t);
+      else ocn_launch(k_hy_flux_z, hy_cols(g), hy_block(), g->ctx->stream, m, t);
       t.n = 0;
     };
     for (size_t f = 0; f < h->fbc.size(); ++f)
@@ -1897,8 +1852,8 @@ static void hydro_flux_bcs(ocn_hydro* h) {
         e.f = fld->d;
         e.a = b.d;
         e.value = b.value;
-        e.sy = (long)fld->T[0];
-        e.sz = (long)fld->T[0] * fld->T[1];
+        e.sy = fld->sy();
+        e.sz = fld->sz();
         e.kind = b.kind;
         e.side = side;
         e.loc = f == 0 ? 1 : f == 1 ? 2 : 0;
@@ -1956,9 +1911,7 @@ static int hydro_implicit(ocn_hydro* h, ocn_hfield* f, int q, double dt) {
   HyImp c;
   if (int rc = hydro_imp_table(h, h->kap[q], dt, &c)) return rc;
   const ocn_hgrid* g = h->lg;
-  dim3 b, gr;
-  hy_cols(g, b, gr);
-  ocn_launch(k_hy_implicit, gr, b, g->ctx->stream, f->d, c, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
+  ocn_launch(k_hy_implicit, hy_cols(g), hy_block(), g->ctx->stream, f->d, c, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], f->sy(), f->sz());
   return OCN_OK;
 }
 static bool hydro_has_implicit(const ocn_hydro* h) {
@@ -1997,9 +1950,9 @@ static IfsOp ifs_op(const ocn_ifs* s, double dt) {
 // sum!(Q, A * u) of one velocity component (A = Ax with arow = Δyᶠᶜ, Ay with Δxᶜᶠ) into the free surface's rows of u's grid (off)
 static void ifs_vsum_launch(ocn_hfield* Q, long off, const ocn_hfield* u, const double* arow) {
   const ocn_hgrid* g = u->g;
-  dim3 blk(64, 4, 1), gr((u->S[0] + 63) / 64, (u->S[1] + 3) / 4, 1);
+  const dim3 blk = hy_block(), gr((u->S[0] + 63) / 64, (u->S[1] + 3) / 4, 1);
   ocn_launch(k_ifs_vsum, gr, blk, g->ctx->stream, Q->d + off, (const double*)u->d, arow, (const double*)g->dzc, u->S[0], u->S[1], g->N[2], g->H[0],
-             g->H[1], g->H[2], (long)u->T[0], (long)u->T[0] * u->T[1], (long)Q->T[0]);
+             g->H[1], g->H[2], u->sy(), u->sz(), Q->sy());
 }
 // fill_halo_regions!(∫ᶻQ), the right-hand side, solve!(η, ...) and fill_halo_regions!(η) (implicit_free_surface.jl:137-155): the
 // iterations go out in batches, the first sized by the last solve's count, and the host reads the stop flag once per batch
@@ -2079,10 +2032,8 @@ static void ifs_correct_launch(ocn_hydro* h, double dt) {
   const ocn_hgrid* g = h->lg;
   const ocn_ifs* s = h->ifs;
   ocn_hfield *u = h->u, *v = h->v;
-  dim3 blk(64, 4, 1), gr((g->N[0] + 63) / 64, (g->N[1] + 3) / 4, 1);
-  ocn_launch(k_ifs_correct, gr, blk, g->ctx->stream, u->d, v->d, (const double*)s->eta->d + h->offE, (const double*)g->dxfc, (const double*)g->dycf,
-             s->grav * dt, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)u->T[0], (long)u->T[0] * u->T[1], (long)v->T[0],
-             (long)v->T[0] * v->T[1], (long)s->eta->T[0]);
+  ocn_launch(k_ifs_correct, hy_cols(g), hy_block(), g->ctx->stream, u->d, v->d, (const double*)s->eta->d + h->offE, (const double*)g->dxfc,
+             (const double*)g->dycf, s->grav * dt, g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], u->sy(), u->sz(), v->sy(), v->sz(), s->eta->sy());
 }
 // every band's rows of ∫ᶻQ to every other rank (hydro_allgather_rows for the implicit free surface)
 static int ifs_allgather_rows(ocn_hydro* h) {
@@ -2117,45 +2068,39 @@ static int hydro_fused_tracers(ocn_hydro* h, double dt, double chi, bool* pressu
   const double cn = 1.5 + chi, cm = 0.5 + chi;
   const bool cvc = hydro_cv_implicit_c(h);
   const bool implicit = hydro_has_implicit(h) || cvc;
+  const dim3 b = hy_block(), gr = hy_cols(g);
+#define HY_CV_AB2(LOC)                                                                                                                     \
+  ocn_launch(k_hy_cv_ab2<LOC>, gr, b, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q), \
+             hy_grid(g), f->sy(), f->sz())
   for (size_t q = 0; q < h->c.size(); ++q) {
     if ((int)q == h->bS && h->bT >= 0 && !implicit) continue;      // stepped together with T
+    ocn_hfield* f = h->c[q];
     if ((int)q == h->bT && !implicit) {
-      dim3 b, gr;
-      hy_cols(g, b, gr);
-      ocn_hfield *T = h->c[q], *S = h->bS >= 0 ? h->c[h->bS] : nullptr;
-      ocn_launch(k_hy_tracers, gr, b, ctx->stream, hy_grid(g), h->buoy, T->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, S ? S->d : (double*)nullptr,
+      ocn_hfield* S = hydro_S(h);
+      ocn_launch(k_hy_tracers, gr, b, ctx->stream, hy_grid(g), h->buoy, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, S ? S->d : (double*)nullptr,
                  S ? (const double*)h->gn[2 + h->bS]->d : (const double*)nullptr, S ? h->gm[2 + h->bS]->d : (double*)nullptr, h->pHY->d, dt, cn, cm,
-                 (long)T->T[0], (long)T->T[0] * T->T[1]);
+                 f->sy(), f->sz());
       *pressure_done = true;
     } else {
       if (cvc) {
         // explicit step, G^- <- G^n and the closure's per-column solve in one kernel
-        dim3 b2, g2;
-        hy_cols(g, b2, g2);
-        ocn_hfield* f = h->c[q];
         if (hydro_catke_lin(h, 1 + (int)q))
-          ocn_launch(k_hy_cv_ab2_lin, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                     hydro_catke_lin_arg(h), hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
-        else if (hydro_cv_center(h))
-          ocn_launch(k_hy_cv_ab2<3>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
-        else
-          ocn_launch(k_hy_cv_ab2<0>, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
-                     hy_grid(g), (long)f->T[0], (long)f->T[0] * f->T[1]);
+          ocn_launch(k_hy_cv_ab2_lin, gr, b, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, hydro_cv_solve(h, 1 + (int)q),
+                     hydro_catke_lin_arg(h), hy_grid(g), f->sy(), f->sz());
+        else if (hydro_cv_center(h)) HY_CV_AB2(3);
+        else HY_CV_AB2(0);
       } else if (implicit && (size_t)(1 + q) < h->kap.size() && h->kap[1 + q] != 0.0) {
         // explicit step, G^- <- G^n and the implicit solve in one kernel; the hydrostatic pressure then comes from update_state!'s kernel
         HyImp it;
         if ((rc = hydro_imp_table(h, h->kap[1 + q], dt, &it))) return rc;
-        dim3 b2, g2;
-        hy_cols(g, b2, g2);
-        ocn_hfield* f = h->c[q];
-        ocn_launch(k_hy_ab2_implicit, g2, b2, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, it, g->N[0], g->N[1], g->N[2],
-                   g->H[0], g->H[1], g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1]);
+        ocn_launch(k_hy_ab2_implicit, gr, b, ctx->stream, f->d, (const double*)h->gn[2 + q]->d, h->gm[2 + q]->d, dt, cn, cm, it, g->N[0], g->N[1], g->N[2],
+                   g->H[0], g->H[1], g->H[2], f->sy(), f->sz());
       } else {
-        hy_ab2_launch(h->c[q], h->gn[2 + q], h->gm[2 + q], dt, chi, true);
+        hy_ab2_launch(f, h->gn[2 + q], h->gm[2 + q], dt, chi, true);
       }
     }
   }
+#undef HY_CV_AB2
   return OCN_OK;
 }
 
@@ -2178,6 +2123,26 @@ static int hydro_local_ab2_step(ocn_hydro* h, double dt, double chi) {
   return OCN_OK;
 }
 
+// the AB2 step of u (q = 0) or v (q = 1) with the closure's per-column solve, for the two step drivers: the three column sums of the
+// stepped field land in U, GU and Un (rows of su elements)
+static void hydro_cv_momentum_launch(ocn_hydro* h, int q, double dt, double cn, double cm, double* U, double* GU, double* Un, long su) {
+  const ocn_hgrid* g = h->lg;
+  ocn_hfield* f = q ? h->v : h->u;
+  const HyCvSolve cs = hydro_cv_solve(h, 0);
+#define HY_CV_MOM(LOC)                                                                                                                     \
+  ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), hy_block(), g->ctx->stream, f->d, (const double*)h->gn[q]->d, \
+             h->gm[q]->d, U, GU, Un, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], f->sy(), f->sz(), su)
+  const bool cz = hydro_vk(h)->loc == 1;
+  if (q) {
+    if (cz) HY_CV_MOM(5);
+    else HY_CV_MOM(2);
+  } else {
+    if (cz) HY_CV_MOM(4);
+    else HY_CV_MOM(1);
+  }
+#undef HY_CV_MOM
+}
+
 // time_step! from ab2_step! on for the implicit free surface: the steps of u, v (∫ᶻQ summed in the same pass) and the tracers, the
 // free-surface solve, the correction, G^- <- G^n, update_state!.  fused = 0 issues the reference's kernels one by one (the same bits)
 static int hydro_ifs_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fused) {
@@ -2194,7 +2159,6 @@ static int hydro_ifs_step_after_tendencies(ocn_hydro* h, double dt, double chi, 
     return api_done(ctx, OCN_OK);
   }
   const double cn = 1.5 + chi, cm = 0.5 + chi;
-  dim3 blk(64, 4, 1);
   const bool cvuv = hydro_cv_implicit_uv(h);
   HyImp impv{nullptr, nullptr, nullptr, nullptr};
   const int visc = !cvuv && hydro_has_implicit(h) && h->kap[0] != 0.0;
@@ -2205,26 +2169,13 @@ static int hydro_ifs_step_after_tendencies(ocn_hydro* h, double dt, double chi, 
     const double* arow = q ? g->dxcf : g->dyfc;
     if (cvuv) {
       // the closure's per-column solve as on the split-explicit path (its three column sums land in Q and are overwritten), then ∫ᶻQ
-      const HyCvSolve cs = hydro_cv_solve(h, 0);
-#define HY_CV_MOM(LOC)                                                                                                                     \
-  ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d,       \
-             h->gm[q]->d, Q->d + off, Q->d + off, Q->d + off, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], (long)f->T[0], (long)f->T[0] * f->T[1], \
-             (long)Q->T[0])
-      const bool cz = hydro_vk(h)->loc == 1;
-      if (q) {
-        if (cz) HY_CV_MOM(5);
-        else HY_CV_MOM(2);
-      } else {
-        if (cz) HY_CV_MOM(4);
-        else HY_CV_MOM(1);
-      }
-#undef HY_CV_MOM
+      hydro_cv_momentum_launch(h, q, dt, cn, cm, Q->d + off, Q->d + off, Q->d + off, Q->sy());
       ifs_vsum_launch(Q, off, f, arow);
       continue;
     }
-    ocn_launch(k_hy_momentum_ifs, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d,
-               Q->d + off, arow, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], (long)f->T[0],
-               (long)f->T[0] * f->T[1], (long)Q->T[0], impv, visc);
+    ocn_launch(k_hy_momentum_ifs, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), hy_block(), ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d,
+               Q->d + off, arow, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0], g->H[1], g->H[2], f->sy(), f->sz(),
+               Q->sy(), impv, visc);
   }
   // fill_halo_regions!(velocities) of implicit_free_surface_step!: the stepped faces on a wall become zero before the correction (∫ᶻQ,
   // summed above, has its wall faces zeroed by its own fill)
@@ -2937,7 +2888,6 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
     return api_done(ctx, OCN_OK);
   }
   const double cn = 1.5 + chi, cm = 0.5 + chi;
-  dim3 blk(64, 4, 1);
   const bool cvuv = hydro_cv_implicit_uv(h);
   HyImp impv{nullptr, nullptr, nullptr, nullptr};
   const int visc = !cvuv && hydro_has_implicit(h) && h->kap[0] != 0.0;
@@ -2946,25 +2896,12 @@ int ocn_hydro_step_after_tendencies(ocn_hydro* h, double dt, double chi, int fus
     ocn_hfield *f = q ? h->v : h->u, *U = q ? s->V : s->U, *GU = q ? s->GV : s->GU;
     const long off = q ? h->offV : h->offU;
     if (cvuv) {
-      const HyCvSolve cs = hydro_cv_solve(h, 0);
-#define HY_CV_MOM(LOC)                                                                                                                     \
-  ocn_launch(k_hy_cv_momentum<LOC>, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d,       \
-             h->gm[q]->d, U->d + off, GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, cs, hy_grid(g), f->S[0], f->S[1], (long)f->T[0],         \
-             (long)f->T[0] * f->T[1], (long)U->T[0])
-      const bool cz = hydro_vk(h)->loc == 1;
-      if (q) {
-        if (cz) HY_CV_MOM(5);
-        else HY_CV_MOM(2);
-      } else {
-        if (cz) HY_CV_MOM(4);
-        else HY_CV_MOM(1);
-      }
-#undef HY_CV_MOM
+      hydro_cv_momentum_launch(h, q, dt, cn, cm, U->d + off, GU->d + off, (q ? h->Vn : h->Un) + off, U->sy());
       continue;
     }
-    ocn_launch(k_hy_momentum, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), blk, ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d, U->d + off,
-               GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0], g->H[1],
-               g->H[2], (long)f->T[0], (long)f->T[0] * f->T[1], (long)U->T[0], impv, visc);
+    ocn_launch(k_hy_momentum, dim3((f->S[0] + 63) / 64, (f->S[1] + 3) / 4, 1), hy_block(), ctx->stream, f->d, (const double*)h->gn[q]->d, h->gm[q]->d,
+               U->d + off, GU->d + off, (q ? h->Vn : h->Un) + off, dt, cn, cm, (const double*)g->dzc, f->S[0], f->S[1], g->N[0], g->N[1], g->N[2], g->H[0],
+               g->H[1], g->H[2], f->sy(), f->sz(), U->sy(), impv, visc);
   }
   if ((rc = hydro_allgather_rows(h))) return api_done(ctx, rc);
   hfield_fill(s->U);
@@ -3025,10 +2962,7 @@ static int hydro_constant_tables(ocn_hydro* h) {
       for (const auto& e : h->cconst) have = have || e.first == x;
       if (have) continue;
       double* d = nullptr;
-      if (hipMalloc((void**)&d, n * sizeof(double)) != hipSuccess) {
-        ocn_set_error(ctx, "allocation of %zu bytes failed", n * sizeof(double));
-        return OCN_ENOMEM;
-      }
+      if (int rc = dev_alloc(ctx, &d, n * sizeof(double))) return rc;
       h->cconst.emplace_back(x, d);
       const std::vector<double> host(n, x);
       OCN_HIP_CHECK(ctx, hipMemcpy(d, host.data(), n * sizeof(double), hipMemcpyHostToDevice));
@@ -3164,10 +3098,10 @@ int ocn_hydro_set_horizontal_coefficient_table(ocn_hydro* h, int32_t order, int3
   OCN_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));        // a step already queued may still read the previous values
   if (!tabs[field].a) {
     double *da = nullptr, *db = nullptr;
-    if (hipMalloc((void**)&da, bytes) != hipSuccess || hipMalloc((void**)&db, bytes) != hipSuccess) {
+    int rc;
+    if ((rc = dev_alloc(ctx, &da, bytes)) || (rc = dev_alloc(ctx, &db, bytes))) {
       hipFree(da);
-      ocn_set_error(ctx, "allocation of %zu bytes failed", 2 * bytes);
-      return OCN_ENOMEM;
+      return rc;
     }
     tabs[field] = ocn_hydro::CoefTab{da, db};
   }
@@ -3320,10 +3254,7 @@ int ocn_hydro_set_convective_adjustment(ocn_hydro* h, int32_t discretization, do
     int rc;
     if ((rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.kap)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &h->cv.nu))) return rc;
     const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
-    if (hipMalloc((void**)&h->cv.t, nt * sizeof(double)) != hipSuccess) {
-      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
-      return OCN_ENOMEM;
-    }
+    if ((rc = dev_alloc(ctx, &h->cv.t, nt * sizeof(double)))) return rc;
   }
   h->cv.on = on;
   h->cv.disc = discretization;
@@ -3429,10 +3360,7 @@ int ocn_hydro_set_ri_based_diffusivity(ocn_hydro* h, int32_t discretization, int
   }
   if (on && !rb.t) {
     const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
-    if (hipMalloc((void**)&rb.t, nt * sizeof(double)) != hipSuccess) {
-      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
-      return OCN_ENOMEM;
-    }
+    if (int rc = dev_alloc(ctx, &rb.t, nt * sizeof(double))) return rc;
   }
   rb.on = on;
   rb.disc = discretization;
@@ -3556,10 +3484,7 @@ int ocn_hydro_set_catke(ocn_hydro* h, int32_t on, int32_t discretization, double
         (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_FACE, &k.Ke)) || (rc = hfield_new(g, OCN_CENTER, OCN_CENTER, OCN_CENTER, &k.Le)))
       return rc;
     const size_t nt = (size_t)g->N[0] * g->N[1] * g->N[2];
-    if (hipMalloc((void**)&ck.t, nt * sizeof(double)) != hipSuccess) {
-      ocn_set_error(ctx, "allocation of %zu bytes failed", nt * sizeof(double));
-      return OCN_ENOMEM;
-    }
+    if ((rc = dev_alloc(ctx, &ck.t, nt * sizeof(double)))) return rc;
     // the wall distance of faces 1..Nz + 1: min(depth, height above the bottom) (mixing_length.jl:97-102)
     const int Nz = g->N[2], off = g->z_regular ? g->H[2] : 0;
     std::vector<double> dw((size_t)Nz + 1);
@@ -3569,10 +3494,7 @@ int ocn_hydro_set_catke(ocn_hydro* h, int32_t on, int32_t discretization, double
       dw[K - 1] = std::fmin(top - z, z - bot);
     }
     if ((rc = upload(ctx, dw, &k.dw))) return rc;
-    if (hipMalloc((void**)&k.Qb, (size_t)g->N[0] * g->N[1] * sizeof(double)) != hipSuccess) {
-      ocn_set_error(ctx, "allocation of %zu bytes failed", (size_t)g->N[0] * g->N[1] * sizeof(double));
-      return OCN_ENOMEM;
-    }
+    if ((rc = dev_alloc(ctx, &k.Qb, (size_t)g->N[0] * g->N[1] * sizeof(double)))) return rc;
   }
   k.has_qb = n_flux != 0;
   if (k.has_qb) OCN_HIP_CHECK(ctx, hipMemcpy(k.Qb, top_buoyancy_flux, (size_t)n_flux * sizeof(double), hipMemcpyHostToDevice));
@@ -3686,10 +3608,7 @@ int ocn_hydro_set_isopycnal_diffusivity(ocn_hydro* h, int32_t discretization, do
   const size_t nb = s.er33->n * sizeof(double);
   auto alloc = [&](double** p, size_t bytes) -> int {
     if (*p) return OCN_OK;
-    if (hipMalloc((void**)p, bytes) != hipSuccess) {
-      ocn_set_error(ctx, "allocation of %zu bytes failed", bytes);
-      return OCN_ENOMEM;
-    }
+    if (int rc = dev_alloc(ctx, p, bytes)) return rc;
     return hipMemset(*p, 0, bytes) == hipSuccess ? OCN_OK : OCN_EHIP;
   };
   for (double*& p : s.w)
@@ -3840,14 +3759,18 @@ int ocn_hydro_weno_coefficients(ocn_hydro* h, double* out, int64_t n) {
   return (int)have;
 }
 
-int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
-  if (!h) return OCN_EINVAL;
-  if (h->lg->H[0] < 1 || h->lg->H[1] < 1 || h->lg->H[2] < 1) return OCN_EINVAL;
+// compute_tendencies!: the interior terms, then what each closure adds to them, then the flux boundary conditions
+static void hydro_all_tendencies(ocn_hydro* h) {
   hydro_tendencies(h);
   hydro_horizontal_closures(h);
   hydro_iso_fluxes(h);
   hydro_catke_sources(h);
   hydro_flux_bcs(h);
+}
+int ocn_hydro_calculate_tendencies(ocn_hydro* h) {
+  if (!h) return OCN_EINVAL;
+  if (h->lg->H[0] < 1 || h->lg->H[1] < 1 || h->lg->H[2] < 1) return OCN_EINVAL;
+  hydro_all_tendencies(h);
   return api_done(h->lg->ctx, OCN_OK);
 }
 
@@ -3858,11 +3781,7 @@ int ocn_hydro_time_step(ocn_hydro* h, double dt, int euler) {
   const double chi = euler ? -0.5 : h->chi;
   if (euler)
     for (ocn_hfield* f : h->gm) OCN_ASYNC(hipMemsetAsync(f->d, 0, f->n * sizeof(double), ctx->stream));
-  hydro_tendencies(h);
-  hydro_horizontal_closures(h);
-  hydro_iso_fluxes(h);
-  hydro_catke_sources(h);
-  hydro_flux_bcs(h);
+  hydro_all_tendencies(h);
   return ocn_hydro_step_after_tendencies(h, dt, chi, 1);
 }
 

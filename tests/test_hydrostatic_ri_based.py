@@ -24,7 +24,8 @@ GRIDNAMES = ["sphere", "sector3", "box"]
 KIND = ["hostemu", pytest.param("gpu", marks=pytest.mark.gpu)]
 TAPERS = ["PiecewiseLinear", "Exponential", "HyperbolicTangent"]
 RTOL_TAPER = 4 * np.finfo(float).eps
-BUOY = {"TS": (TS, ("T", "S")), "b": (("b", "b"), ("b", "c")), "none": (None, ("T", "S"))}
+# "TSc" (the cases named ..._3): a third tracer, so the tracer kernels launch a pair (T, S) and then a single tracer (c)
+BUOY = {"TS": (TS, ("T", "S")), "b": (("b", "b"), ("b", "c")), "none": (None, ("T", "S")), "TSc": (TS, ("T", "S", "c"))}
 
 
 @pytest.fixture
@@ -64,7 +65,9 @@ def _closure(H, case, loc, taper):
             "vsd_after": (imp, V(nu=1e-3, kappa=1e-4)),
             "explicit_lap": (L(nu=2e3, kappa=1e3), exp),
             "explicit_tuple": (exp, B(nu=1e12, kappa=5e11), L(nu=2e3, kappa=1e3)),
-            "implicit_tuple": (B(nu=1e12, kappa=5e11), imp, L(nu=2e3, kappa=1e3), V(nu=1e-3, kappa=1e-4))}[case]
+            "explicit_bih": (exp, B(nu=1e12, kappa=5e11)),
+            "implicit_bih": (B(nu=1e12, kappa=5e11), imp),
+            "implicit_tuple": (B(nu=1e12, kappa=5e11), imp, L(nu=2e3, kappa=1e3), V(nu=1e-3, kappa=1e-4))}[case.removesuffix("_3")]
 
 
 def _bcs(H, tracers):
@@ -128,7 +131,7 @@ def _compare(be, gridname, case, loc, taper, buoy="TS", bcs=False, dts=(300.0, 3
     exact = _exact(be, gridname) and taper == "PiecewiseLinear"
     closure = _closure(_lib_H(), case, loc, taper)
     st, so = _pair(be, gridname, closure, buoy, bcs)
-    bih = case in ("explicit_tuple", "implicit_tuple")
+    bih = case.removesuffix("_3") in ("explicit_tuple", "explicit_bih", "implicit_bih", "implicit_tuple")
     what = f"on {gridname} ({case}, {loc}, {taper}, {buoy})"
     fl = st.diffusivity_fields
     assert fl["kappa"].loc[2] == loc
@@ -249,12 +252,17 @@ def test_parity_tuples(kind, gridname, case, loc, ocn, backend, oracle_rb):
     _compare(LibBackend(ocn), gridname, case, loc, "Exponential" if case == "implicit_tuple" else "PiecewiseLinear")
 
 
+# the last five: the instances of the explicit closure's pass with Center coefficients that no other case launches (a viscosity that is
+# biharmonic only, next to the explicit form and to the implicit form's w-shear term; a single tracer alone and with either or both orders)
 @pytest.mark.parametrize("gridname,case,loc", [("sector3", "implicit", "Face"), ("sector3", "explicit_tuple", "Center"),
-                                               ("box", "with_vsd", "Center"), ("box", "explicit_lap", "Face")])
+                                               ("box", "with_vsd", "Center"), ("box", "explicit_lap", "Face"),
+                                               ("sector3", "explicit_bih_3", "Center"), ("sector3", "implicit_bih", "Center"),
+                                               ("box", "explicit_3", "Center"), ("box", "explicit_lap_3", "Center"),
+                                               ("sector3", "explicit_tuple_3", "Center")])
 @pytest.mark.parametrize("kind", KIND)
 def test_parity_with_flux_conditions_and_varying_dt(kind, gridname, case, loc, ocn, backend, oracle_rb):
     _run_kind(kind, backend)
-    _compare(LibBackend(ocn), gridname, case, loc, "PiecewiseLinear", "TS", bcs=True, dts=(300.0, 240.0))
+    _compare(LibBackend(ocn), gridname, case, loc, "PiecewiseLinear", "TSc" if case.endswith("_3") else "TS", bcs=True, dts=(300.0, 240.0))
 
 
 @pytest.mark.parametrize("loc", ["Face", "Center"])
