@@ -22,6 +22,8 @@ BC_DEFAULT, BC_PERIODIC, BC_NOFLUX, BC_FLUX, BC_VALUE, BC_GRADIENT, BC_IMPENETRA
 WEST, EAST, SOUTH, NORTH, BOTTOM, TOP = range(6)
 F_U, F_V, F_W, F_PHY, F_PNHS, F_GN, F_GM, F_TRACER, F_NU, F_KAPPA = 0, 1, 2, 3, 4, 16, 32, 48, 64, 72
 
+FEATURE_STOKES_DRIFT = 1
+
 ERRORS = {-1: "OCN_EINVAL", -2: "OCN_ENOMEM", -3: "OCN_EHIP", -4: "OCN_EUNSUPPORTED", -5: "OCN_ESTATE"}
 
 
@@ -102,6 +104,9 @@ def load():
         "ocn_grid_destroy": (None, [P]),
         "ocn_model_create": (I, [P, C.POINTER(ModelDesc), C.POINTER(P)]),
         "ocn_model_create_smagorinsky_lilly": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.POINTER(P)]),
+        "ocn_model_create_with": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(P)]),
+        "ocn_model_set_stokes_drift": (I, [P, I, PD, PD, PD, PD, PD, PD, I]),
+        "ocn_model_stage_times": (I, [P, D, C.POINTER(C.c_double * 3), C.POINTER(C.c_int32)]),
         "ocn_model_destroy": (None, [P]),
         "ocn_model_halo": (I, [P, C.POINTER(C.c_int32 * 3)]),
         "ocn_model_path": (I, [P, C.c_char_p, C.c_size_t]),

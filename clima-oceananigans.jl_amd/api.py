@@ -108,6 +108,27 @@ class FPlane:
         self.f = float(f)
 
 
+class UniformStokesDrift:
+    """``UniformStokesDrift(; ∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ)`` (StokesDrift.jl:46-62): four functions ``f(z, t)``; ``None`` is the
+    reference's ``addzero``.  The functions are evaluated on the host at the z nodes and at the clock time of each stage; the
+    kernels read the resulting tables."""
+
+    def __init__(self, dz_us=None, dz_vs=None, dt_us=None, dt_vs=None):
+        for n, f in (("dz_us", dz_us), ("dz_vs", dz_vs), ("dt_us", dt_us), ("dt_vs", dt_vs)):
+            if f is not None and not callable(f):
+                raise TypeError(f"UniformStokesDrift: {n} must be a function of (z, t) or None")
+        self.dz_us, self.dz_vs, self.dt_us, self.dt_vs = dz_us, dz_vs, dt_us, dt_vs
+
+    def tables(self, zC, zF, t):
+        """the six tables of ocn_model_set_stokes_drift at time t, one (6, Nz) array"""
+        def ev(f, z):
+            if f is None:
+                return np.zeros(z.size)
+            return np.array([float(f(float(zk), float(t))) for zk in z], dtype=np.float64)
+        return np.ascontiguousarray([ev(self.dz_us, zC), ev(self.dz_vs, zC), ev(self.dz_us, zF), ev(self.dz_vs, zF),
+                                     ev(self.dt_us, zC), ev(self.dt_vs, zC)], dtype=np.float64)
+
+
 class BuoyancyTracer:
     tracers = ("b",)
 
@@ -344,8 +365,15 @@ class NonhydrostaticModel:
     timestepper)`` (Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203)."""
 
     def __init__(self, grid, advection=None, buoyancy=None, coriolis=None, closure=None,
-                 boundary_conditions=None, tracers=(), timestepper="QuasiAdamsBashforth2", chi=0.1):
+                 boundary_conditions=None, tracers=(), timestepper="QuasiAdamsBashforth2", chi=0.1, stokes_drift=None):
         self.grid, self.ctx, self.lib = grid, grid.ctx, grid.ctx.lib
+        if stokes_drift is not None and not isinstance(stokes_drift, UniformStokesDrift):
+            raise TypeError("stokes_drift must be a UniformStokesDrift or None")
+        if stokes_drift is not None and grid.topo[2] == Flat:
+            raise ValueError("UniformStokesDrift on a grid with a Flat z is outside the path")
+        self.stokes_drift = stokes_drift
+        self.stokes_uploads = 0            # table sets sent to the library so far (one per stage slot whose contents changed)
+        self._stokes_sent = [None] * 3     # what each stage slot holds
         if isinstance(tracers, str):
             tracers = (tracers,)
         self.tracer_names = tuple(tracers)
@@ -431,8 +459,10 @@ class NonhydrostaticModel:
                 fill(d.bcs[names.index(fname)], side, bc)
         self.desc = d
         self.h = C.c_void_p()
-        if smag is None:
+        if smag is None and stokes_drift is None:
             check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
+        elif smag is None:
+            check(self.lib.ocn_model_create_with(grid.h, C.byref(d), None, L.FEATURE_STOKES_DRIFT, C.byref(self.h)), self.ctx.h)
         else:
             sd = L.SmagorinskyLillyDesc()
             sd.C, sd.Cb = smag.C, smag.Cb
@@ -440,7 +470,11 @@ class NonhydrostaticModel:
                 if isinstance(smag.Pr, dict) and n not in smag.Pr:
                     raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
                 sd.Pr[i] = smag.Pr_of(n)
-            check(self.lib.ocn_model_create_smagorinsky_lilly(grid.h, C.byref(d), C.byref(sd), C.byref(self.h)), self.ctx.h)
+            if stokes_drift is None:
+                check(self.lib.ocn_model_create_smagorinsky_lilly(grid.h, C.byref(d), C.byref(sd), C.byref(self.h)), self.ctx.h)
+            else:
+                check(self.lib.ocn_model_create_with(grid.h, C.byref(d), C.byref(sd), L.FEATURE_STOKES_DRIFT, C.byref(self.h)),
+                      self.ctx.h)
         H = (C.c_int32 * 3)()
         check(self.lib.ocn_model_halo(self.h, C.byref(H)), self.ctx.h)
         self.halo = tuple(H)
@@ -466,6 +500,33 @@ class NonhydrostaticModel:
                 self.h = C.c_void_p()
         except Exception:
             pass
+
+    # ---- UniformStokesDrift: host evaluation of the drift's functions into the library's stage slots ------------------------
+    def _stokes_set(self, slot, t):
+        _, _, Z = self.nodes("u")
+        _, _, ZF = self.nodes("w")
+        Nz = self.grid.Nz
+        tab = self.stokes_drift.tables(Z.ravel()[:Nz], ZF.ravel()[:Nz], t)
+        if self._stokes_sent[slot] is not None and np.array_equal(tab, self._stokes_sent[slot]):
+            return
+        PD = C.POINTER(C.c_double)
+        ptr = [tab[i].ctypes.data_as(PD) for i in range(6)]
+        check(self.lib.ocn_model_set_stokes_drift(self.h, slot, *ptr, Nz), self.ctx.h)
+        self._stokes_sent[slot] = tab
+        self.stokes_uploads += 1
+
+    def stage_times(self, dt):
+        """clock times at which the stages of ``time_step(model, dt)`` compute their tendencies (the library's own sums)"""
+        t, n = (C.c_double * 3)(), C.c_int32()
+        check(self.lib.ocn_model_stage_times(self.h, float(dt), C.byref(t), C.byref(n)), self.ctx.h)
+        return [t[i] for i in range(n.value)]
+
+    def refresh_stokes_drift(self):
+        """for the kernel-by-kernel verbs (``ocn_compute_tendencies`` ...): evaluate the drift at ``model.time`` into the slot
+        of the current stage.  ``time_step`` does this by itself for every stage of the step."""
+        if self.stokes_drift is not None:
+            t, _, stage = self.clock
+            self._stokes_set(stage - 1, t)
 
     @property
     def kernel_path(self):
@@ -544,6 +605,9 @@ class NonhydrostaticModel:
 
 def time_step(model, dt, euler=False):
     """``time_step!(model, Δt; euler=false)``."""
+    if getattr(model, "stokes_drift", None) is not None:
+        for slot, t in enumerate(model.stage_times(dt)):   # outside any graph capture; only slots whose tables changed are sent
+            model._stokes_set(slot, t)
     check(model.lib.ocn_time_step(model.h, float(dt), int(bool(euler))), model.ctx.h)
 
 

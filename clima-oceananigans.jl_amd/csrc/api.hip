@@ -876,9 +876,17 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-// ocn_model_create and ocn_model_create_smagorinsky_lilly (smag != null) share this body
-static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
+// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null) and ocn_model_create_with share this body
+static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes, ocn_model** out) {
   ocn_ctx* ctx = g->ctx;
+  if (stokes && g->topo[2] == OCN_FLAT) {
+    ocn_set_error(ctx, "UniformStokesDrift on a grid with a Flat z is outside the path (its terms are vertical averages)");
+    return OCN_EUNSUPPORTED;
+  }
+  if (stokes && (g->dist || g->dist_y || ctx->nranks > 1)) {
+    ocn_set_error(ctx, "UniformStokesDrift on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) is not supported");
+    return OCN_EUNSUPPORTED;
+  }
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
   if (desc->advection < OCN_ADV_NONE || desc->advection > OCN_ADV_U3) return OCN_EINVAL;
   if (desc->closure == OCN_CLOSURE_AMD && (g->topo[0] == OCN_FLAT || g->topo[1] == OCN_FLAT || g->topo[2] == OCN_FLAT)) {
@@ -1019,6 +1027,15 @@ static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smago
     ocn_model_destroy(m);
     return OCN_ENOMEM;
   }
+  if (stokes) {
+    const size_t nb = (size_t)3 * 6 * g->N[2] * sizeof(double);
+    m->stokes = 1;
+    m->stokes_stage = (double*)calloc(1, nb);
+    if (!m->stokes_stage || hipMalloc((void**)&m->stokes_dev, nb) != hipSuccess || hipMemset(m->stokes_dev, 0, nb) != hipSuccess) {
+      ocn_model_destroy(m);
+      return OCN_ENOMEM;
+    }
+  }
   fused_read_knobs(m);
   m->fast_path = fused_available(m) ? 1 : 0;
   m->bz_fast = (!m->fast_path && fused_bz_available(m)) ? 1 : 0;
@@ -1057,11 +1074,24 @@ extern "C" {
 int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
   if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-  return model_create(g, desc, nullptr, out);
+  return model_create(g, desc, nullptr, false, out);
 }
 
 int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
-  if (!g || !desc || !smag || !out) return OCN_EINVAL;
+  return smag ? ocn_model_create_with(g, desc, smag, 0, out) : OCN_EINVAL;
+}
+
+int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features, ocn_model** out) {
+  if (!g || !desc || !out) return OCN_EINVAL;
+  if (features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
+    ocn_set_error(g->ctx, "ocn_model_create_with: unknown feature bits 0x%x", features);
+    return OCN_EINVAL;
+  }
+  const bool stokes = (features & OCN_FEATURE_STOKES_DRIFT) != 0;
+  if (!smag) {
+    if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
+    return model_create(g, desc, nullptr, stokes, out);
+  }
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
   if (desc->closure != OCN_CLOSURE_NONE && desc->closure != OCN_CLOSURE_SCALAR) {
@@ -1093,7 +1123,59 @@ int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, 
     ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
     return OCN_EINVAL;
   }
-  return model_create(g, desc, smag, out);
+  return model_create(g, desc, smag, stokes, out);
+}
+
+int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,
+                               const double* dz_vs_f, const double* dt_us_c, const double* dt_vs_c, int n) {
+  if (!m) return OCN_EINVAL;
+  if (!m->stokes) {
+    ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: the model was created without Stokes drift (ocn_model_create_with, OCN_FEATURE_STOKES_DRIFT)");
+    return OCN_ESTATE;
+  }
+  if (stage < 0 || stage > 2) {
+    ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: stage %d is outside 0..2", stage);
+    return OCN_EINVAL;
+  }
+  const int Nz = m->gd.Nz;
+  if (n != Nz) {
+    ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: tables of %d entries on a grid of Nz = %d levels", n, Nz);
+    return OCN_EINVAL;
+  }
+  // library-owned staging: the caller's arrays are free again on return; a null table is the reference's addzero
+  const double* src[6] = {dz_us_c, dz_vs_c, dz_us_f, dz_vs_f, dt_us_c, dt_vs_c};
+  double* st = m->stokes_stage + (size_t)stage * 6 * Nz;
+  // the slot's previous upload may still be reading the staging memory: wait for that copy alone (it was queued ahead of the
+  // step that used it, so this does not wait for the stream to drain)
+  if (m->stokes_ev[stage]) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(m->stokes_ev[stage]));
+  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&m->stokes_ev[stage]));
+  for (int t = 0; t < 6; ++t) {
+    if (src[t]) memcpy(st + (size_t)t * Nz, src[t], (size_t)Nz * sizeof(double));
+    else memset(st + (size_t)t * Nz, 0, (size_t)Nz * sizeof(double));
+  }
+  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->stokes_dev + (size_t)stage * 6 * Nz, st, (size_t)6 * Nz * sizeof(double), hipMemcpyHostToDevice,
+                                       m->ctx->stream));
+  OCN_HIP_CHECK(m->ctx, hipEventRecord(m->stokes_ev[stage], m->ctx->stream));
+  return api_ret(m->ctx, OCN_OK);
+}
+
+int ocn_model_stage_times(const ocn_model* m, double dt, double times[3], int32_t* nstages) {
+  if (!m || !times || !nstages) return OCN_EINVAL;
+  times[0] = times[1] = times[2] = m->time;
+  if (m->d.stepper == OCN_STEPPER_AB2) {
+    *nstages = 1;
+    return OCN_OK;
+  }
+  // the clock of time_step_rk3: m->time += sdt[s] after each stage, the same products and sums
+  const double g1 = 8.0 / 15.0, g2 = 5.0 / 12.0, z2 = -17.0 / 60.0;
+  const double sdt[2] = {g1 * dt, (g2 + z2) * dt};
+  double t = m->time;
+  for (int s = 0; s < 2; ++s) {
+    t += sdt[s];
+    times[s + 1] = t;
+  }
+  *nstages = 3;
+  return OCN_OK;
 }
 
 void ocn_model_destroy(ocn_model* m) {
@@ -1125,6 +1207,10 @@ void ocn_model_destroy(ocn_model* m) {
   hipFree(m->phi_below);
   hipFree(m->amd_tab);
   hipFree(m->smag_tab);
+  hipFree(m->stokes_dev);
+  for (hipEvent_t e : m->stokes_ev)
+    if (e) hipEventDestroy(e);
+  free(m->stokes_stage);
   hipFree(m->ypack_s);
   hipFree(m->ypack_r);
   poisson_destroy(m->solver);

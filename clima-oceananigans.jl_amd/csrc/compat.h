@@ -94,6 +94,10 @@ __device__ __forceinline__ double ocn_shfl_xor16(double x) {
 // a value that is the same in every lane of the wave, moved to a scalar register: branches on it are scalar branches
 // (s_setprio and the LDS-DMA base in M0 are scalar state -- behind a "divergent" branch they would execute regardless of EXEC)
 #define OCN_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
+// a double from a table that no kernel writes, at a wave-uniform address: read through the constant address space, so the load is
+// a scalar one (s_load_dwordx2) even after the kernel's own global stores, which the compiler cannot tell apart from the table
+typedef const __attribute__((address_space(4))) double ocn_const_double;
+#define OCN_SLOAD(p) (*(ocn_const_double*)(p))
 
 #else
 // ------------------------------------------------------------------------------------------------
@@ -190,6 +194,7 @@ static inline void __syncthreads() { g_emu_barrier.wait(); }
 // wave-level primitives, emulated with one OS thread per GPU thread (every thread of the block must make the call)
 #define OCN_WAVE 64
 #define OCN_UNIFORM(x) (x)
+#define OCN_SLOAD(p) (*(p))
 #define OCN_LD_NT(p) (*(p))                /* cache policies mean nothing on the host */
 #define OCN_ST_NT(p, v) ((void)(*(p) = (v)))
 static inline void ocn_glds16(const void* src_lane, void* dst_wave_base, int lane) {

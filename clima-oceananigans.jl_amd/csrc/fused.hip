@@ -529,9 +529,16 @@ struct RestArgs {
   double nu, f;                         // constant viscosity (nue == null), Coriolis parameter
   double nu0;                           // added to nue: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
   int closure, coriolis, ntiles;
+  const double* sk;                     // STOKES: the stage's UniformStokesDrift tables (internal.h stokes_slot)
 };
 
-template <int BX, int BY, bool ZB, bool NU0>   // NU0: a.nu0 is added to the eddy viscosity
+// STOKES: UniformStokesDrift (StokesDrift.jl:66-80).  G_u, G_v of level k-1 need I_z(I_x w), I_z(I_y w) over faces k-1 and k; G_w of
+// face k needs I_z(I_x u), I_z(I_y v) over levels k-1 and k.  Level k is in the slab; of level k-1 the four horizontal two-point
+// averages (w with its west / south neighbour, u with its east, v with its north neighbour) are carried in registers next to
+// up / vp / wp -- in the reference's own association, I_z of I_x -- and start every segment from the parent arrays.  The east and
+// north values are read from the slab (never a lane shift): wave seams, the x wrap and the ghost row need no special case.  The
+// drift's shear and rate of change are per-level scalars of the stage's tables.
+template <int BX, int BY, bool ZB, bool NU0, bool STOKES = false>   // NU0: a.nu0 is added to the eddy viscosity
 __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
   const double nu0 = NU0 ? a.nu0 : 0.0;
   constexpr int T = BX * BY, NR = BY + 1, SX = BX + 6;      // rows j0-1 .. j0+BY-1; columns -3 .. Nx+2 (the parent row)
@@ -589,6 +596,13 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
     double up = ldo(a.u, cb), vp = ldo(a.v, cb), wp = ldo(a.w, cb);
     double ncp = amd ? (NU0 ? ldo(a.nue, cb) + nu0 : ldo(a.nue, cb)) : a.nu, nwp = amd ? (NU0 ? ldo(a.nue, cb - sxb) + nu0 : ldo(a.nue, cb - sxb)) : a.nu, nsp = amd ? (NU0 ? ldo(a.nue, cb - syb) + nu0 : ldo(a.nue, cb - syb)) : a.nu;
     double hu = 0, hv = 0, hw = 0, bu = 0, bv = 0, bw = 0;
+    double wxp = 0, wyp = 0, uxp = 0, vyp = 0;       // STOKES: I_x w, I_y w, I_x u, I_y v of the level below
+    if (STOKES) {
+      wxp = 0.5 * (ldo(a.w, cb - sxb) + wp);
+      wyp = 0.5 * (ldo(a.w, cb - syb) + wp);
+      uxp = 0.5 * (up + ldo(a.u, cb + sxb));
+      vyp = 0.5 * (vp + ldo(a.v, cb + syb));
+    }
     __syncthreads();
     dma(k0, 0);
     for (int k = k0; k <= k1; ++k) {
@@ -640,6 +654,13 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
         fyn[1 * T + tid] = t22;
         fyn[2 * T + tid] = t23;
       }
+      double wx = 0, wy = 0, ux = 0, vy = 0;
+      if (STOKES && full) {                           // row ty + 1 of the slab exists for output rows only
+        wx = 0.5 * (RS(2, 0, -1) + wc);
+        wy = 0.5 * (RS(2, -1, 0) + wc);
+        ux = 0.5 * (uc + RS(0, 0, 1));
+        vy = 0.5 * (vc + RS(1, 1, 0));
+      }
       double e0 = 0, e1 = 0, e2 = 0;
       if (!last) {
         e0 = ocn_shfl_next(t11);
@@ -656,6 +677,11 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
         if (k > k0) {                                 // level k-1: z differences with this level's bottom stresses on top
           const unsigned cm1 = c - szb;
           const double rzc = ZB ? g_rdzc(g, k - 1) : g.rdz, rzfm = ZB ? g_rdzf(g, k - 1) : g.rdz;
+          if (STOKES) {
+            const double* sk = a.sk + (k - 1);
+            hu += 0.5 * (wxp + wx) * OCN_SLOAD(sk) + OCN_SLOAD(sk + 4 * g.Nz);
+            hv += 0.5 * (wyp + wy) * OCN_SLOAD(sk + g.Nz) + OCN_SLOAD(sk + 5 * g.Nz);
+          }
           sto(a.gu, cm1, hu + 2.0 * ((t13 - bu) * rzc));
           sto(a.gv, cm1, hv + 2.0 * ((t23 - bv) * rzc));
           sto(a.gw, cm1, hw + 2.0 * ((t33 - bw) * rzfm));   // w at face k-1: tau33 at centre k-1 (here) minus centre k-2 (carried)
@@ -675,6 +701,7 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
           hu = cu + 2.0 * fma(xedge ? -t11 : e0 - t11, rdx, -t12 * rdy);
           hv = cv + 2.0 * fma(xedge ? -t12 : e1 - t12, rdx, -t22 * rdy);
           hw = 2.0 * fma(xedge ? -t13 : e2 - t13, rdx, -t23 * rdy);
+          if (STOKES) hw -= 0.5 * (uxp + ux) * OCN_SLOAD(a.sk + 2 * g.Nz + k) + 0.5 * (vyp + vy) * OCN_SLOAD(a.sk + 3 * g.Nz + k);
           bu = t13;
           bv = t23;
           bw = t33;
@@ -682,6 +709,7 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
       }
       up = uc; vp = vc; wp = wc;
       ncp = nc; nwp = nw; nsp = ns;
+      if (STOKES) { wxp = wx; wyp = wy; uxp = ux; vyp = vy; }
     }
   }
 #undef RS
@@ -1034,7 +1062,8 @@ static const char* tiled_blocker(const ocn_model* m) {
   return nullptr;
 }
 
-bool fused_available(const ocn_model* m) {
+// the all-in-one periodic path would serve the model if it had no Stokes drift
+static bool fused_available_but_for_stokes(const ocn_model* m) {
   const ocn_grid* g = m->g;
   if (g->topo[0] != OCN_PERIODIC || g->topo[1] != OCN_PERIODIC || g->topo[2] != OCN_PERIODIC) return false;
   if (!g->z_regular) return false;
@@ -1044,6 +1073,11 @@ bool fused_available(const ocn_model* m) {
   if (tiled_blocker(m)) return false;
   if (getenv("OCNHIP_NO_FUSED")) return false;   // model creation only
   return true;
+}
+
+bool fused_available(const ocn_model* m) {
+  if (m->stokes) return false;   // UniformStokesDrift: its terms live in k_rest4 / k_tend_uvw, like Coriolis
+  return fused_available_but_for_stokes(m);
 }
 
 static bool tend4_asel(const ocn_model* m, bool plain);
@@ -1067,6 +1101,11 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
   else if (why) snprintf(buf, n, "general kernels: %s", why);
   else if (m->g->topo[0] == OCN_FLAT || m->g->topo[1] == OCN_FLAT) snprintf(buf, n, "general kernels: Flat x / y slices are outside the tiled kernels");
   else snprintf(buf, n, "general kernels (tiled path disabled or not applicable to this topology / decomposition)");
+  if (m->stokes && fused_available_but_for_stokes(m)) {   // the drift alone keeps this model off the all-in-one path
+    const size_t l = strlen(buf);
+    snprintf(buf + l, n - l, "; not the all-in-one periodic path: Stokes drift terms are served by %s",
+             rest4_ok(m) ? "k_rest4" : "the general kernel");
+  }
   if (m->d.closure == OCN_CLOSURE_SMAG) {
     const size_t l = strlen(buf);
     snprintf(buf + l, n - l, "; nu_e: %s", smag_tiled_ok(m) ? "tiled kernel (k_smag_nu)" : "one thread per cell (k_smag_nu_cell)");
@@ -1334,6 +1373,7 @@ bool launch_rest4(ocn_model* m) {
   a.f = m->d.f;
   a.closure = m->d.closure;
   a.coriolis = m->d.coriolis_fplane;
+  a.sk = stokes_slot(m);
   int bx = gd.Nx <= 64 ? 64 : gd.Nx <= 128 ? 128 : 256;
   int by = bx == 256 ? 4 : 8;
 #ifdef OCN_HOST_EMU
@@ -1353,7 +1393,8 @@ bool launch_rest4(ocn_model* m) {
   const dim3 blk(bx, by, 1), grd(nseg, 1, 1);
   hipStream_t s = m->ctx->stream;
   const bool zb = m->g->topo[2] == OCN_BOUNDED;
-#define REST4N(BXV, BYV, N0) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0>, grd, blk, s, gd, a); }
+#define REST4S(BXV, BYV, N0, SK) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0, SK>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0, SK>, grd, blk, s, gd, a); }
+#define REST4N(BXV, BYV, N0) { if (a.sk) REST4S(BXV, BYV, N0, true) else REST4S(BXV, BYV, N0, false) }
 #define REST4(BXV, BYV) { if (a.nu0 != 0.0) REST4N(BXV, BYV, true) else REST4N(BXV, BYV, false) }
 #ifdef OCN_HOST_EMU
   if (bx == 16) REST4(16, 4) else
@@ -1361,6 +1402,7 @@ bool launch_rest4(ocn_model* m) {
   if (bx == 256) REST4(256, 4) else if (bx == 128) REST4(128, 8) else REST4(64, 8)
 #undef REST4
 #undef REST4N
+#undef REST4S
   return true;
 }
 

@@ -155,6 +155,13 @@ struct ocn_model {
   bool pnhs_deferred = false;
   bool pnhs_escaped = false;     // ocn_field_device_ptr(pNHS) was called: reads can no longer be seen, every projection stores
   int knob_eager_pressure = 0;   // OCNHIP_EAGER_PRESSURE=1: every projection stores pNHS (callers who read it after every step)
+  // UniformStokesDrift: the drift's four functions of (z, t) arrive as host tables (ocn_model_set_stokes_drift), one slot per
+  // stage.  Slot s holds six runs of Nz doubles: d_z u^s, d_z v^s at centres, the same at faces k = 1..Nz, d_t u^s, d_t v^s at
+  // centres.  The device addresses never change, so a captured step graph keeps reading the current contents.
+  int stokes = 0;                // created with Stokes drift (decides the path: never the all-in-one periodic one)
+  double* stokes_dev = nullptr;  // [3][6][Nz]
+  double* stokes_stage = nullptr;   // host staging of the same shape (the source of the asynchronous uploads)
+  hipEvent_t stokes_ev[3] = {nullptr, nullptr, nullptr};   // recorded behind each slot's upload
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
 };
@@ -164,6 +171,11 @@ inline Field& pred_v(ocn_model* m) { return m->pred_active ? m->vs : m->v; }
 inline Field& pred_w(ocn_model* m) { return m->pred_active ? m->ws : m->w; }
 // the model's projections leave the pNHS store to pnhs_materialize (see pnhs_deferred)
 inline bool pnhs_lazy(const ocn_model* m) { return m->fast_path && !m->g->dist && !m->knob_eager_pressure && !m->pnhs_escaped; }
+
+// the Stokes-drift tables a tendency launch reads: the slot of the current stage (null: no Stokes drift)
+inline const double* stokes_slot(const ocn_model* m) {
+  return m->stokes ? m->stokes_dev + (size_t)(m->stage - 1) * 6 * m->gd.Nz : nullptr;
+}
 
 Field* model_field(ocn_model* m, int id);
 

@@ -22,6 +22,7 @@ struct Phys {
   const double* pH;     // interior pointer or null
   const double* nu_e;   // AMD, SmagorinskyLilly
   double nu0;           // added to nu_e: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
+  const double* sk;     // UniformStokesDrift tables of this stage (internal.h stokes_slot) or null
   int buoyancy, bi, Ti, Si;
   double g, alpha, beta;
 };
@@ -122,6 +123,15 @@ __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, con
   if (ph.pH) {
     gu -= (ph.pH[c] - ph.pH[c - 1]) * rdx;
     gv -= (ph.pH[c] - ph.pH[c - sy]) * rdy;
+  }
+  // ---- UniformStokesDrift (StokesDrift.jl:66-80): (curl U^s) x U + d_t U^s, the drift's shear and rate of change read from the
+  // stage's tables (k is wave-uniform: scalar loads); I_xz = I_z(I_x .), as interpolation_operators.jl:62-68 ----
+  if (ph.sk) {
+    const double* sk = ph.sk + k;
+    gu += 0.5 * (0.5 * (w[c - 1] + w[c]) + 0.5 * (w[c - 1 + sz] + w[c + sz])) * OCN_SLOAD(sk) + OCN_SLOAD(sk + 4 * Nz);
+    gv += 0.5 * (0.5 * (w[c - sy] + w[c]) + 0.5 * (w[c - sy + sz] + w[c + sz])) * OCN_SLOAD(sk + Nz) + OCN_SLOAD(sk + 5 * Nz);
+    gw -= 0.5 * (0.5 * (u[c - sz] + u[c + 1 - sz]) + 0.5 * (u[c] + u[c + 1])) * OCN_SLOAD(sk + 2 * Nz) +
+          0.5 * (0.5 * (v[c - sz] + v[c + sy - sz]) + 0.5 * (v[c] + v[c + sy])) * OCN_SLOAD(sk + 3 * Nz);
   }
   // ---- viscous stress divergence (closure_kernel_operators.jl:22-41; fluxes -2 nu Sigma) ----
   if (ph.closure != OCN_CLOSURE_NONE) {
@@ -248,6 +258,7 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
   ph.nu_e = m->nu_e.present ? m->nu_e.interior() : nullptr;
   const bool smag = m->d.closure == OCN_CLOSURE_SMAG;
   ph.nu0 = smag ? m->d.nu : 0.0;
+  ph.sk = stokes_slot(m);
   static const dim3 b = tuned_block("OCNHIP_TEND_BLOCK", dim3(64, 4, 1));
   const dim3 gr = grid3(g, b);
   const double *u = m->u.interior(), *v = m->v.interior(), *w = m->w.interior();

@@ -183,6 +183,29 @@ typedef struct ocn_smagorinsky_lilly_desc {
   double Pr[OCN_MAX_TRACERS];   /* turbulent Prandtl number per tracer (1.0)                              */
 } ocn_smagorinsky_lilly_desc;
 int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out);
+/* The general creator (additive: OCN_ABI_VERSION and every struct layout are unchanged).  smag == NULL: as ocn_model_create;
+ * else as ocn_model_create_smagorinsky_lilly.  features: OCN_FEATURE_* bits.
+ *
+ * OCN_FEATURE_STOKES_DRIFT -- NonhydrostaticModel(; stokes_drift = UniformStokesDrift(∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ)), StokesDrift.jl:46-80:
+ *   G_u += I_xz(w) ∂z_uˢ(z_c, t) + ∂t_uˢ(z_c, t),  G_v += I_yz(w) ∂z_vˢ(z_c, t) + ∂t_vˢ(z_c, t),
+ *   G_w -= I_xz(u) ∂z_uˢ(z_f, t) + I_yz(v) ∂z_vˢ(z_f, t).
+ * The four functions of (z, t) cannot cross this boundary; the caller evaluates them into tables (ocn_model_set_stokes_drift).  It is
+ * a creation-time property because it decides the kernels (never the all-in-one periodic path; ocn_model_path says so).  All
+ * tables are zero until set.  OCN_EUNSUPPORTED: Flat z; a distributed grid (z- or y-slabs, more than one rank,
+ * OCNHIP_FORCE_DIST). */
+#define OCN_FEATURE_STOKES_DRIFT 1u
+int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features, ocn_model** out);
+/* Tables of the drift for the tendency evaluation of stage `stage` (0..2; QuasiAdamsBashforth2 uses 0; the kernel-by-kernel
+ * verbs read slot `stage of ocn_clock` - 1): ∂z_uˢ, ∂z_vˢ at znode(Center, k), the same two at znode(Face, k), ∂t_uˢ, ∂t_vˢ at
+ * znode(Center, k), k = 1..Nz, n = Nz entries each; a NULL table is all zeros (the reference's addzero).  The values are
+ * copied before the call returns and uploaded on the model's stream; the device addresses of a slot never change, so a
+ * replayed step graph reads whatever was set last.  OCN_ESTATE: a model created without the feature; OCN_EINVAL: stage
+ * outside 0..2, n != Nz. */
+int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,
+                               const double* dz_vs_f, const double* dt_us_c, const double* dt_vs_c, int n);
+/* clock.time at which each stage of the next ocn_time_step(m, dt, .) computes its tendencies, accumulated exactly as the
+ * steppers do (runge_kutta_3.jl:81-152: the clock ticks between stages): *nstages = 1 (AB2) or 3 (RK3). */
+int ocn_model_stage_times(const ocn_model* m, double dt, double times[3], int32_t* nstages);
 void ocn_model_destroy(ocn_model* m);
 /* which kernels serve this model, and if not the fastest ones, why (e.g. "general kernels: parent arrays of 2 GiB or
  * more exceed the tiled kernels' 32-bit byte offsets").  Writes at most n bytes incl. the terminating 0. */

@@ -92,8 +92,8 @@ function bc_of(bc, keep)
 end
 
 function ocn_model(arch::ROCmGPU, gridh, m)                                             # m: the fields NonhydrostaticModel(...) assembled
-    isempty(m.forcing) && m.stokes_drift === nothing && isempty(m.background_fields) ||
-        error("forcings, Stokes drift and background fields are Julia closures: outside the C ABI")
+    isempty(m.forcing) && isempty(m.background_fields) || error("forcings and background fields are Julia closures: outside the C ABI")
+    m.stokes_drift === nothing || m.stokes_drift isa UniformStokesDrift || error("stokes_drift: only UniformStokesDrift is on the path")
     names = keys(m.tracers); nt = length(names)
     pad(t) = ntuple(i -> i <= length(t) ? Float64(t[i]) : 0.0, MAXTR)
     cl = m.closure
@@ -122,7 +122,12 @@ function ocn_model(arch::ROCmGPU, gridh, m)                                     
                      closure == 2 ? sides(m.diffusivity_fields.νₑ) : none,
                      ntuple(i -> (closure == 2 && i <= nt) ? sides(m.diffusivity_fields.κₑ[i]) : none, MAXTR))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    GC.@preserve keep check(ccall((:ocn_model_create, libocnhip), Cint, (Ptr{Cvoid}, Ref{ModelDesc}, Ref{Ptr{Cvoid}}), gridh, desc, h), arch.ctx)
+    if m.stokes_drift === nothing
+        GC.@preserve keep check(ccall((:ocn_model_create, libocnhip), Cint, (Ptr{Cvoid}, Ref{ModelDesc}, Ref{Ptr{Cvoid}}), gridh, desc, h), arch.ctx)
+    else  # a creation-time property: it decides the kernels.  OCN_FEATURE_STOKES_DRIFT = 1; a SmagorinskyLilly desc goes where C_NULL is
+        GC.@preserve keep check(ccall((:ocn_model_create_with, libocnhip), Cint, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ref{Ptr{Cvoid}}),
+                                      gridh, desc, C_NULL, UInt32(1), h), arch.ctx)
+    end
     return h[]
 end
 
@@ -158,8 +163,35 @@ end
 const RM = NonhydrostaticModel{<:Any, <:Any, <:ROCmGPU}   # models living on ROCmGPU (handle kept in model.auxiliary_fields.ocn)
 handle(m) = m.auxiliary_fields.ocn
 
+# stokes_drift = UniformStokesDrift(∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ) (StokesDrift.jl:46-80): the four functions of (z, t) stay in Julia and
+# are evaluated into six tables of Nz numbers per stage -- at znode(Center, k) and znode(Face, k), k = 1..Nz, and at the clock
+# times ocn_model_stage_times returns (the library's own sums: RungeKutta3 ticks between its stages).  A slot is sent only when
+# its tables changed, so a drift constant in time costs nothing per step.  Not run: no Julia toolchain exists where this was written.
+function set_stokes_drift!(model::RM, slot, t, sent)
+    sw, grid, Nz = model.stokes_drift, model.grid, model.grid.Nz
+    zc = [znode(Center(), k, grid) for k in 1:Nz]; zf = [znode(Face(), k, grid) for k in 1:Nz]
+    tabs = (Float64[sw.∂z_uˢ(z, t) for z in zc], Float64[sw.∂z_vˢ(z, t) for z in zc], Float64[sw.∂z_uˢ(z, t) for z in zf],
+            Float64[sw.∂z_vˢ(z, t) for z in zf], Float64[sw.∂t_uˢ(z, t) for z in zc], Float64[sw.∂t_vˢ(z, t) for z in zc])
+    sent[slot + 1] == tabs && return nothing
+    check(ccall((:ocn_model_set_stokes_drift, libocnhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Cint), handle(model), slot, tabs..., Nz), model.architecture.ctx)
+    sent[slot + 1] = tabs
+    return nothing
+end
+function refresh_stokes_drift!(model::RM, Δt)       # before ocn_time_step; model.auxiliary_fields.stokes_sent = Any[nothing, nothing, nothing]
+    model.stokes_drift === nothing && return nothing
+    times = zeros(3); n = Ref(Int32(0))
+    check(ccall((:ocn_model_stage_times, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ref{Int32}), handle(model), Δt, times, n))
+    for s in 1:n[]
+        set_stokes_drift!(model, s - 1, times[s], model.auxiliary_fields.stokes_sent)
+    end
+end
+# the kernel-by-kernel verbs read the slot of the current stage: set_stokes_drift!(model, model.clock.stage - 1, model.clock.time, sent)
+# before calculate_tendencies!(model)
+
 # TimeSteppers/quasi_adams_bashforth_2.jl:70-104 and runge_kutta_3.jl:81-152 -- preferred, coarsest overload
 function time_step!(model::RM, Δt; euler=false)
+    refresh_stokes_drift!(model, Δt)
     check(ccall((:ocn_time_step, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Cint), handle(model), Δt, euler), model.architecture.ctx)
     # clock mirrors ocn_clock (TimeSteppers/clock.jl:48-60)
     t = Ref(0.0); it = Ref(Int64(0)); st = Ref(Int32(0))
