@@ -87,6 +87,14 @@ __device__ __forceinline__ double ocn_shfl_xor16(double x) {
   return b.d;
 }
 #define OCN_WAVE 64
+// LDS written by lanes of a wave is read by other lanes of the SAME wave: the wave's LDS operations complete in order, the
+// compiler only has to keep them in order
+#define OCN_WAVE_SYNC()                                      \
+  do {                                                       \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
+    __builtin_amdgcn_wave_barrier();                         \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
+  } while (0)
 // Cache policy of streams a kernel touches ONCE (the `nt` modifier of global_load / global_store): the line is not worth an
 // L2 slot that data with a second use could keep (k_tend4's slab rows).  Same addressing forms as the plain access.
 #define OCN_LD_NT(p) __builtin_nontemporal_load(p)
@@ -193,6 +201,7 @@ static inline void __syncthreads() { g_emu_barrier.wait(); }
 
 // wave-level primitives, emulated with one OS thread per GPU thread (every thread of the block must make the call)
 #define OCN_WAVE 64
+#define OCN_WAVE_SYNC() g_emu_barrier.wait()
 #define OCN_UNIFORM(x) (x)
 #define OCN_SLOAD(p) (*(p))
 #define OCN_LD_NT(p) (*(p))                /* cache policies mean nothing on the host */

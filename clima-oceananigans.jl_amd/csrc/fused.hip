@@ -1092,8 +1092,9 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
     const char* pform = m->g->dist ? "" : pnhs_lazy(m) ? " (pressure written on demand)"
                         : m->pnhs_escaped ? " (pressure stored by every projection: its device pointer was handed out)"
                                           : " (pressure stored by every projection)";
-    snprintf(buf, n, "all-in-one periodic path: k_tend4%s + fused Poisson passes + k_project%s%s", asel ? " (address-selected stencils)" : "",
-             pform, !m->g->dist ? "" : ov ? "; z-slabs, halo planes travel under the next interior tendency launch"
+    const char* yform = !poisson_custom_xy(m) || m->g->dist ? "" : poisson_split_y(m) ? " (split-y form: three passes)" : " (five-pass form)";
+    snprintf(buf, n, "all-in-one periodic path: k_tend4%s + fused Poisson passes%s + k_project%s%s", asel ? " (address-selected stencils)" : "",
+             yform, pform, !m->g->dist ? "" : ov ? "; z-slabs, halo planes travel under the next interior tendency launch"
                                    : "; z-slabs, halo exchange on the model's stream");
   }
   else if (m->bz_fast) snprintf(buf, n, "tiled advection + update (k_tend4, REST) on top of the %s other terms",
@@ -1146,6 +1147,8 @@ struct FusedShape {
 //   OCNHIP_NO_SMAG_TILED=1  SmagorinskyLilly: the one-thread-per-cell nu_e kernel where k_smag_nu would apply (tests, A/B)
 //   OCNHIP_TEND4_VSEL=1   k_tend4 reads six stencil values and selects five where the address-selected form exists (tests,
 //                         same-build A/B; see rec_a in the kernel)
+//   OCNHIP_SPLIT_Y=0      periodic pressure solve in its five-pass form (separate y passes, library inverse x) where the split-y
+//                         form would serve (tests, A/B)
 //   OCNHIP_EAGER_PRESSURE=1  every projection of the all-in-one path stores pNHS (for callers who read the pressure after every
 //                         step; tests, same-build A/B; see ocn_model::pnhs_deferred)
 void fused_read_knobs(ocn_model* m) {
@@ -1154,6 +1157,7 @@ void fused_read_knobs(ocn_model* m) {
   m->knob_no_dma = env("OCNHIP_NO_LDS_DMA", 0);
   m->knob_no_tracer3 = env("OCNHIP_NO_TRACER3", 0);
   m->knob_xfft_team = env("OCNHIP_XFFT_TEAM", 0);
+  m->knob_split_y = env("OCNHIP_SPLIT_Y", 1);
   m->knob_overlap = env("OCNHIP_OVERLAP", -1);   // -1: on when there is more than one rank
   m->knob_overlap_cus = env("OCNHIP_OVERLAP_CUS", 16);
   m->knob_graph = env("OCNHIP_NO_GRAPH", 0) ? 0 : 1;   // whole-step hipGraphs of the general path (api.hip step_graphed)

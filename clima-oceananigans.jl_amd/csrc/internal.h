@@ -143,6 +143,7 @@ struct ocn_model {
   // it needs through fused_exchange_phi), so their exchange -- 2 x H planes per step -- is deferred until somebody can look:
   // ocn_sync, ocn_fill_halos(pNHS) and ocn_field_download(pNHS), all collective on slab runs (api.hip pnhs_refresh)
   bool pnhs_halo_stale = false;
+  int knob_split_y = 1;      // OCNHIP_SPLIT_Y=0: the periodic solve keeps its two y passes where the split-y form would serve (tests, A/B)
   int knob_xfft_team = 0;    // OCNHIP_XFFT_TEAM=1: the fused rhs + x transform loads in team order (the older variant; tests)
   int knob_graph = 1;        // OCNHIP_NO_GRAPH=1 clears it (model creation)
   int knob_tend4_vsel = 0;   // OCNHIP_TEND4_VSEL=1: k_tend4 selects stencil values, not addresses, everywhere (tests, A/B)
@@ -240,6 +241,13 @@ void zsolve_destroy(void* z);
 void zsolve_run(ocn_ctx* ctx, void* z, void* spec, int Nz, const double* lz, double norm, long zero_col);
 void yfft_run(ocn_ctx* ctx, void* z, void* spec, int Nxh, int Ny, int Nz, int inverse);
 void xfft_rhs_run(ocn_model* m, void* z, void* spec, double dt, int extra_plane = 0);
+// split-y form (Ny = 256): y stage 1 in the x passes, y stage 2 in the z pass; the spectrum between them has the row pitch split_y_pitch
+bool split_y_ok(int Nx, int Ny, int Nz);
+int split_y_pitch(int Nx);
+void xfft_rhs_sy_run(ocn_model* m, void* tw, void* spec, double dt);
+void zsolve_sy_run(ocn_ctx* ctx, void* zs, void* spec, int Nx, int Nz, const double* lz, double norm);
+void xinv_sy_run(ocn_ctx* ctx, void* tw, const void* spec, double* real, int Nx, int Ny, int Nz);
+bool poisson_split_y(const ocn_model* m);       // the split-y form serves the model's pressure solve
 bool poisson_local_wstar(const ocn_model* m);   // z-slab runs: the w* term above the slab enters in spectral space, no w* plane exchange
 bool fft_size_ok(int n);   // 128, 256, 512: sizes of the custom transform passes
 bool zsolve_size_ok(int n);   // those and 320, 384: sizes of the fused z stage

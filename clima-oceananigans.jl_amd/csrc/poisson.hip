@@ -42,6 +42,7 @@ struct PoissonSolver {
   void* zsl = nullptr;                     // slab runs: transpose-free z stage (zslab.hip)
   double dz2 = 0;
   bool cxy = false;                        // custom x / y passes (zfft.hip): rhs fused into the x transform
+  bool split_y = false;                    // cxy with the y transform folded into the x and z passes (zfft.hip k_xfft_rhs_sy)
   bool cxy_bz = false;                     // Bounded z: the same passes around the tridiagonal sweeps (poisson_run_from_predictor_bz)
   // z-slabs, Green's-function z stage, custom x / y passes: the w* plane of this rank's first level is transformed here and
   // enters the convolution as a source one level below the slab (zslab.hip `bel`) -- the lower neighbour never needs the plane
@@ -157,6 +158,11 @@ PoissonSolver* poisson_create(ocn_model* m) {
     s->Nyl = s->Ny / s->R;
   }
   size_t nr = (size_t)s->Nx * s->Ny * s->Nz, nc = (size_t)s->Nxh * s->Ny * s->Nz;
+  // single-rank triply periodic boxes the split-y form serves: its spectrum rows are padded (the other paths keep the pitch Nxh).
+  // The buffer is sized here, before the z stage and the custom passes are decided: it is the larger one whenever the form MAY
+  // serve, also where a knob below then keeps it from serving.  OCNHIP_XFFT_TEAM=1 asks for a variant of the five-pass x kernel.
+  const bool may_split = m->knob_split_y && !m->knob_xfft_team && !g->dist && g->topo[2] == OCN_PERIODIC && g->z_regular && split_y_ok(s->Nx, s->Ny, s->Nz);
+  if (may_split) nc = (size_t)split_y_pitch(s->Nx) * s->Ny * s->Nz;
   const size_t xr = g->dist ? (size_t)s->Nx * s->Ny : 0, xc = g->dist ? (size_t)s->Nxh * s->Ny : 0;   // one plane more on z-slabs
   if (hipMalloc((void**)&s->rhs, (nr + xr) * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&s->spec, (nc + xc) * sizeof(double2_)) != hipSuccess) {
@@ -211,6 +217,7 @@ PoissonSolver* poisson_create(ocn_model* m) {
     std::vector<double> one(1, 0.0);
     s->tw = zsolve_create(m->ctx, one, one);
     s->cxy = s->tw != nullptr && (s->zs || s->zsl);
+    s->split_y = may_split && s->cxy && s->zs;
     if (s->cxy && g->dist && s->zsl && !(getenv("OCNHIP_WSTAR_EXCHANGE") && atoi(getenv("OCNHIP_WSTAR_EXCHANGE")) != 0)) {
       s->bplane = s->spec + nc;
       s->local_phi = !(getenv("OCNHIP_PHI_EXCHANGE") && atoi(getenv("OCNHIP_PHI_EXCHANGE")) != 0);
@@ -1123,6 +1130,7 @@ static int run_solver(ocn_model* m) {
 int poisson_run(ocn_model* m) { return run_solver(m); }
 
 bool poisson_custom_xy(const ocn_model* m) { return m->solver && m->solver->cxy; }
+bool poisson_split_y(const ocn_model* m) { return m->solver && m->solver->split_y; }
 bool poisson_local_wstar(const ocn_model* m) { return m->solver && m->solver->bplane != nullptr; }
 bool poisson_local_phi_below(const ocn_model* m) { return m->solver && m->solver->bplane != nullptr && m->solver->local_phi; }
 const double* poisson_phi_below(const ocn_model* m) { return m->solver->rhs + (size_t)m->solver->Nx * m->solver->Ny * m->solver->Nz; }
@@ -1156,6 +1164,21 @@ static void emu_xinv(PoissonSolver* s, const double2_* spec = nullptr, double* o
 // Leaves the solution in the solver's real buffer (like run_solver).
 int poisson_run_from_predictor(ocn_model* m, double dt) {
   PoissonSolver* s = m->solver;
+  if (s->split_y) {   // three passes: x + y stage 1, y stage 2 + z + its inverse, inverse y stage 1 + x
+    {
+      ProfScope ps(m->ctx, "fft_forward");
+      xfft_rhs_sy_run(m, s->tw, s->spec, dt);
+    }
+    {
+      ProfScope ps(m->ctx, "spectral_solve");
+      zsolve_sy_run(m->ctx, s->zs, s->spec, s->Nx, s->Nz, s->lz, 1.0 / ((double)s->Nx * s->Ny * s->Nz));
+    }
+    {
+      ProfScope ps(m->ctx, "fft_backward");
+      xinv_sy_run(m->ctx, s->tw, s->spec, s->rhs, s->Nx, s->Ny, s->Nz);
+    }
+    return OCN_OK;
+  }
   const int xp = s->bplane ? 1 : 0, ip = (s->bplane && s->local_phi) ? 1 : 0;   // planes more in the forward / inverse passes
   {
     ProfScope ps(m->ctx, "fft_forward");

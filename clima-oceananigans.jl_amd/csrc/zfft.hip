@@ -91,10 +91,12 @@ template <int S> OCN_DEVFN void dft8(cd* v) {
 // Columns per workgroup: 32 (N = 128), 16 (256), 8 (512); `c` is the column slot of the thread INCLUDING the half for
 // N = 512 (c = col + 8 h), so the 256-point network below serves both.
 #define SMN (16 * (256 + 32))
-template <int N> struct FftGeo {
+// T: threads of the workgroup (256 everywhere but the split-y passes below, whose workgroups hold 32 lines or columns); the
+// LDS images grow with it: SMN * T / 256 doubles
+template <int N, int T = 256> struct FftGeo {
   static constexpr int M = N / 16;                   // threads per transform
-  static constexpr int C = 256 / M;                  // columns per workgroup
-  static constexpr int CS = N == 512 ? 16 : C;       // column slots of the LDS images (N = 512: column + 8 half)
+  static constexpr int C = T / M;                    // columns per workgroup
+  static constexpr int CS = N == 512 ? 2 * C : C;    // column slots of the LDS images (N = 512: column + C half)
   static constexpr int RS = N == 128 ? 8 : 16;       // threads per team in the LDS images
   static constexpr int K1S = RS * CS + CS;           // padded stride of the k1 index: rows of different r hit different banks
 };
@@ -102,8 +104,8 @@ template <int N> struct FftGeo {
 // all threads of the workgroup take part (barriers inside)
 // XL: the x pass, whose lanes run over r first (the transformed direction is the contiguous one): image [k1][c][r] with an
 // odd k1 stride, conflict-free for its writes (r consecutive) and its reads (k1 = r consecutive: stride 257 words)
-template <int N, int S, bool XL = false> OCN_DEVFN void fft_stage2(double* sm, cd* v, int r, int c, const cd* tw) {
-  typedef FftGeo<N> G;
+template <int N, int S, bool XL = false, int T = 256> OCN_DEVFN void fft_stage2(double* sm, cd* v, int r, int c, const cd* tw) {
+  typedef FftGeo<N, T> G;
   constexpr int KX = G::RS * G::CS + 1;
   constexpr int TS = 512 / (N == 512 ? 256 : N);     // table stride of the inner transform's roots
   // twiddles W^(r k1) of the inner transform (n2 = r)
@@ -151,20 +153,21 @@ template <int N, int S, bool XL = false> OCN_DEVFN void fft_stage2(double* sm, c
 }
 
 // the 16 points of the partner thread (same column and r, other half) through LDS; barriers inside
-OCN_DEVFN void fft512_partner(double* sm, const cd* v, cd* p, int r, int c) {
-  const int me = r * 16 + c, other = r * 16 + (c ^ 8);          // [q][r][c]: consecutive lanes, consecutive words
+template <int T = 256> OCN_DEVFN void fft512_partner(double* sm, const cd* v, cd* p, int r, int c) {
+  constexpr int C = FftGeo<512, T>::C;
+  const int me = r * 2 * C + c, other = r * 2 * C + (c ^ C);    // [q][r][c]: consecutive lanes, consecutive words
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) sm[q * 256 + me] = v[q].x;
+  for (int q = 0; q < 16; ++q) sm[q * T + me] = v[q].x;
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) p[q].x = sm[q * 256 + other];
+  for (int q = 0; q < 16; ++q) p[q].x = sm[q * T + other];
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) sm[q * 256 + me] = v[q].y;
+  for (int q = 0; q < 16; ++q) sm[q * T + me] = v[q].y;
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) p[q].y = sm[q * 256 + other];
+  for (int q = 0; q < 16; ++q) p[q].y = sm[q * T + other];
   __syncthreads();
 }
 
@@ -172,14 +175,27 @@ OCN_DEVFN void fft512_partner(double* sm, const cd* v, cd* p, int r, int c) {
 // or 16; out: see the table above.  Unnormalised; S = +1: exp(-i ...), S = -1: exp(+i ...).
 // XLANE: the x pass -- real input, and its thread layout puts the partner 16 lanes away in the same wave: the partner's
 // 16 real values come by ds_bpermute instead of five barriers around an LDS image
-template <int N, int S, bool XLANE = false> OCN_DEVFN void fft_fwd(double* sm, cd* v, int r, int c, const cd* tw) {
-  if (N == 512) {
+// CPLX: complex input in the x pass's thread layout (the inverse x pass): both components come by ds_bpermute
+template <int N, int S, bool XLANE = false, int T = 256, bool CPLX = false> OCN_DEVFN void fft_fwd(double* sm, cd* v, int r, int c, const cd* tw) {
+  if (N == 512 && XLANE && CPLX) {
+    const int h = (c / FftGeo<512, T>::C) & 1;
+#pragma unroll
+    for (int n1 = 0; n1 < 16; ++n1) {
+      const cd p = cd{ocn_shfl_xor16(v[n1].x), ocn_shfl_xor16(v[n1].y)};
+      if (h == 0) v[n1] = cadd(v[n1], p);
+      else {
+        cd w = tw[(r + 16 * n1) & 511];
+        if (S < 0) w.y = -w.y;
+        v[n1] = cmul(csub(p, v[n1]), w);
+      }
+    }
+  } else if (N == 512) {
     cd p[16];
     if (XLANE) {
 #pragma unroll
       for (int q = 0; q < 16; ++q) p[q] = cd{ocn_shfl_xor16(v[q].x), 0.0};
-    } else fft512_partner(sm, v, p, r, c);
-    const int h = (c >> 3) & 1;
+    } else fft512_partner<T>(sm, v, p, r, c);
+    const int h = (c / FftGeo<512, T>::C) & 1;
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) {
       if (h == 0) v[n1] = cadd(v[n1], p[n1]);                    // x[n] + x[n + 256]
@@ -191,13 +207,13 @@ template <int N, int S, bool XLANE = false> OCN_DEVFN void fft_fwd(double* sm, c
     }
   }
   dft16<S>(v);
-  fft_stage2<N, S, XLANE>(sm, v, r, c, tw);
+  fft_stage2<N, S, XLANE, T>(sm, v, r, c, tw);
 }
 
 // the same network run backwards: from the spectral layout of fft_fwd<N, +1> back to v[n1] = x[r + M' n1 (+ 256 h)],
 // unnormalised (x N)
-template <int N> OCN_DEVFN void fft_back(double* sm, cd* v, int r, int c, const cd* tw) {
-  typedef FftGeo<N> G;
+template <int N, int T = 256> OCN_DEVFN void fft_back(double* sm, cd* v, int r, int c, const cd* tw) {
+  typedef FftGeo<N, T> G;
   constexpr int TS = 512 / (N == 512 ? 256 : N);
   if (N == 128) {
     dft8<-1>(v);
@@ -249,7 +265,7 @@ template <int N> OCN_DEVFN void fft_back(double* sm, cd* v, int r, int c, const 
   dft16<-1>(v);                                                  // r = n2 again: v[n1] = u_h[r + 16 n1]
   if (N == 512) {
     // undo the decimation step: u0 = x[n] + x[n+256], u1 = (x[n] - x[n+256]) W^n  ->  2 x[n] = u0 + u1 conj(W^n), ...
-    const int h = (c >> 3) & 1;
+    const int h = (c / FftGeo<512, T>::C) & 1;
     if (h == 1) {
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) {
@@ -259,7 +275,7 @@ template <int N> OCN_DEVFN void fft_back(double* sm, cd* v, int r, int c, const 
       }
     }
     cd p[16];
-    fft512_partner(sm, v, p, r, c);
+    fft512_partner<T>(sm, v, p, r, c);
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) v[n1] = h == 0 ? cadd(v[n1], p[n1]) : csub(p[n1], v[n1]);   // 2 x[n], 2 x[n + 256]
   }
@@ -267,19 +283,19 @@ template <int N> OCN_DEVFN void fft_back(double* sm, cd* v, int r, int c, const 
 
 // thread -> (r, column slot c, element index of v[q] along the transformed direction) for data whose COLUMNS are adjacent
 // in memory (y and z passes): t = c + CS * r
-template <int N> OCN_DEVFN void team_of(int t, int& r, int& c, int& col) {
-  typedef FftGeo<N> G;
+template <int N, int T = 256> OCN_DEVFN void team_of(int t, int& r, int& c, int& col) {
+  typedef FftGeo<N, T> G;
   c = t % G::CS;
   r = t / G::CS;
-  col = N == 512 ? (c & 7) : c;
+  col = N == 512 ? c % G::C : c;
 }
 // position along the transformed direction of v[n1] on the way in (physical side) ...
-template <int N> OCN_DEVFN int pos_in(int r, int c, int n1) {
-  return N == 128 ? r + 8 * n1 : N == 256 ? r + 16 * n1 : r + 16 * n1 + 256 * ((c >> 3) & 1);
+template <int N, int T = 256> OCN_DEVFN int pos_in(int r, int c, int n1) {
+  return N == 128 ? r + 8 * n1 : N == 256 ? r + 16 * n1 : r + 16 * n1 + 256 * ((c / FftGeo<N, T>::C) & 1);
 }
 // ... and of v[q] on the way out (spectral side)
-template <int N> OCN_DEVFN int pos_out(int r, int c, int q) {
-  return N == 128 ? (r + 8 * (q >> 3)) + 16 * (q & 7) : N == 256 ? r + 16 * q : 2 * (r + 16 * q) + ((c >> 3) & 1);
+template <int N, int T = 256> OCN_DEVFN int pos_out(int r, int c, int q) {
+  return N == 128 ? (r + 8 * (q >> 3)) + 16 * (q & 7) : N == 256 ? r + 16 * q : 2 * (r + 16 * q) + ((c / FftGeo<N, T>::C) & 1);
 }
 
 // ---- fused z stage: forward transform, eigenvalue division, backward transform in one pass ------------------------------
@@ -590,6 +606,234 @@ __global__ void __launch_bounds__(256) k_xfft_rhs(GridDev g, const double* __res
   }
 }
 
+// ---- split-y form of the periodic solve (Ny = 256): the y transform rides in the x and z passes ---------------------------
+// The 256-point y transform is a four-step one, j = ry + 8 n1 and ky = k1 + 32 k2:
+//   stage 1   T(ry, k1) = W256^(ry k1) sum_n1 x[ry + 8 n1] W32^(n1 k1)    needs the 32 rows of one residue ry, any kx, one level
+//   stage 2   Y[k1 + 32 k2] = sum_ry T(ry, k1) W8^(ry k2)                 needs the 8 residues of one (kx, k1), any level
+// so stage 1 runs inside the x passes, whose workgroups hold whole x lines of the 32 rows j = ry + 8 n1 of a level, and stage 2
+// inside the z pass, whose workgroups hold whole z columns of 8 residues x CW consecutive kx of one k1: three passes over the
+// spectrum instead of five.  Between the passes the spectrum is T(kx; k1, ry; k) at kx + P (k1 + 32 ry + 256 k) with the row
+// pitch P = Nx / 2 + 8 (a multiple of 8: every row starts on a 128-byte line); kx >= Nx / 2 + 1 of a row is never touched.
+#define SY_R1 32
+#define SY_R2 8
+int split_y_pitch(int Nx) { return Nx / 2 + 8; }
+bool split_y_ok(int Nx, int Ny, int Nz) { return Ny == SY_R1 * SY_R2 && fft_size_ok(Nx) && fft_size_ok(Nz); }
+
+// place of T(kx; k1, ry; k): rows of pitch P.  (The 8 residues of four consecutive kx side by side, 512 contiguous bytes per level
+// for the z pass, was measured and lost: the x passes then move 64-byte pieces, profiles/split_y_notes.md.)
+OCN_DEVFN long sy_at(int P, int kx, int k1, int ry, long k) { return kx + (long)P * (k1 + SY_R1 * (ry + SY_R2 * k)); }
+
+// one half of a 32-point transform: in v[k] = x[k] + (-1)^p x[k + 16], out v[m] = X[p + 2 m]
+template <int S> OCN_DEVFN void dft32_half(cd* v, int p, const cd* tw) {
+  if (p) {
+#pragma unroll
+    for (int k = 1; k < 16; ++k) {
+      cd w = tw[16 * k];                                           // W32^k
+      if (S < 0) w.y = -w.y;
+      v[k] = cmul(v[k], w);
+    }
+  }
+  dft16<S>(v);
+}
+
+// forward x pass with y stage 1.  One workgroup = the 32 lines j = ry + 8 n1 of one level, 2 N threads (N / 16 per line).
+// Workgroups b, b + 8, ... share an XCD: the 8 residues of a level follow each other there, so the rows j + 1 that the
+// neighbouring residue reads as its own come out of that L2.
+template <int N>
+__global__ void __launch_bounds__(2 * N) k_xfft_rhs_sy(GridDev g, const double* __restrict__ us, const double* __restrict__ vs,
+                                                       const double* __restrict__ ws, double rdt, int zwrap,
+                                                       cd* __restrict__ spec, const cd* __restrict__ tw) {
+  constexpr int T = 2 * N, M = N / 16, NH = N / 2 + 1, P = N / 2 + 8;
+  OCN_SHARED double sm[SMN * (T / 256)];
+  const int t = threadIdx.x;
+  const int rr = t % M, ln = t / M;                  // position inside the team; line n1 of the workgroup
+  const int r = N == 512 ? rr & 15 : rr;
+  const int c = N == 512 ? ln + SY_R1 * (rr >> 4) : ln;
+  const int b = blockIdx.x;
+  const int ry = (b / 8) % SY_R2, k = (b / (8 * SY_R2)) * 8 + b % 8;
+  const long sy = g.sy, sz = g.sz;
+  const double rdz = 1.0 / g.dz;
+  constexpr int LP = N + 16;
+  static_assert(SY_R1 * LP <= SMN * (T / 256) && 2 * SY_R1 * NH <= SMN * (T / 256), "tiles must fit the transform's LDS buffer");
+  cd v[16];
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    const int e = t + T * m;
+    const int l2 = e / N, i = e - l2 * N;
+    const int j = ry + SY_R2 * l2;
+    const long row = j * sy + k * sz;
+    const long rown = ((j + 1 == g.Ny) ? 0 : j + 1) * sy + k * sz;
+    const long rowt = (zwrap && k + 1 == g.Nz) ? j * sy : j * sy + (k + 1) * sz;
+    const int ie = (i + 1 == g.Nx) ? 0 : i + 1;
+    sm[l2 * LP + i] = ((us[row + ie] - us[row + i]) * g.rdx + (vs[rown + i] - vs[row + i]) * g.rdy + (ws[rowt + i] - ws[row + i]) * rdz) * rdt;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) v[n1] = {sm[ln * LP + pos_in<N, T>(r, c, n1)], 0.0};
+  __syncthreads();
+  fft_fwd<N, 1, true, T>(sm, v, r, c, tw);
+  __syncthreads();
+  cd* ls = (cd*)sm;                                  // half spectra of the 32 lines: ls[n1 * NH + kx]
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int kmin = N == 128 ? 8 * (q >> 3) + 16 * (q & 7) : N == 256 ? 16 * q : 32 * q;
+    if (kmin > N / 2) continue;
+    const int kx = pos_out<N, T>(r, c, q);
+    if (kx <= N / 2) ls[ln * NH + kx] = v[q];
+  }
+  __syncthreads();
+  // y stage 1: two threads per kx, each one half of the 32-point transform over the lines
+  const int p = t / NH, kx = t - p * NH;
+  if (p < 2) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const cd a = ls[q * NH + kx], bb = ls[(q + 16) * NH + kx];
+      v[q] = p ? csub(a, bb) : cadd(a, bb);
+    }
+    dft32_half<1>(v, p, tw);
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      const int k1 = p + 2 * m;
+      spec[sy_at(P, kx, k1, ry, k)] = cmul(v[m], tw[(2 * ry * k1) & 511]);    // W256^(ry k1)
+    }
+  }
+}
+
+// y stage 2 (S = +1) or its inverse inside the z pass.  In: the thread of residue slot ry holds v[n1] of column T(kx; k1, ry); the 8
+// threads of a (kx, r) swap so that slot a holds points n1 = 2 a, 2 a + 1 of all 8 residues, transform them, and swap back:
+// out: slot s holds v[n1] of column ky = k1 + 32 s.  The 8 threads are lanes of one wave (t = kxs + CW slot + ...), so only the
+// first and the last barrier are the workgroup's.
+template <int S, int T> OCN_DEVFN void sy_stage2(double* sm, cd* v, int t, int cw, int ry) {
+  constexpr int ST = T + 2;                          // level pitch of the image: the 8 x CW readers of a level pair hit different banks
+  const int t0 = t - cw * ry;                        // the thread of slot 0
+  const int lv = 2 * ry;
+  cd u[16];                                          // u[8 e + q]: point 2 a + e of residue q
+  __syncthreads();
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) sm[n1 * ST + t] = v[n1].x;
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) u[q].x = sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)];
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) sm[n1 * ST + t] = v[n1].y;
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) u[q].y = sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)];
+  dft8<S>(u);
+  dft8<S>(u + 8);
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)] = u[q].x;
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) v[n1].x = sm[n1 * ST + t];
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)] = u[q].y;
+  OCN_WAVE_SYNC();
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) v[n1].y = sm[n1 * ST + t];
+  __syncthreads();
+}
+
+// z stage with y stage 2 in front of and behind it.  One workgroup = 8 residues x CW consecutive kx of one k1, all N levels.
+// lxy[kx + Nxh ky] as in k_zsolve; the zeroed mode is kx = ky = kz = 0.
+template <int N, int T>
+__global__ void __launch_bounds__(T) k_zsolve_sy(cd* __restrict__ a, int Nxh, int P, const double* __restrict__ lxy,
+                                                 const double* __restrict__ lz, const cd* __restrict__ tw, double norm) {
+  typedef FftGeo<N, T> G;
+  constexpr int CW = G::C / SY_R2;
+  static_assert(G::CS <= 64 && 16 * (T + 2) <= SMN * (T / 256), "the residues of a column group must be lanes of one wave");
+  OCN_SHARED double sm[SMN * (T / 256)];
+  int r, c, col;
+  team_of<N, T>(threadIdx.x, r, c, col);
+  const int kxs = col % CW, ry = col / CW;
+  const int tiles = (Nxh + CW - 1) / CW;            // the padding of a row (kx >= Nxh) gets no workgroup
+  // neighbouring kx tiles share 128-byte lines: handed out XCD-major as in k_yfft
+  const int nblk = SY_R1 * tiles;
+  const int b = ((int)blockIdx.x % 8) * (nblk / 8) + (int)blockIdx.x / 8;
+  const int tile = b % tiles, k1 = b / tiles;
+  const int kx = tile * CW + kxs;
+  const bool ok = kx < Nxh;
+  const long ncol = (long)P * SY_R1 * SY_R2;
+  cd* col0 = a + sy_at(P, kx, k1, ry, 0);
+  cd v[16];
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) v[n1] = ok ? col0[ncol * pos_in<N, T>(r, c, n1)] : cd{0, 0};
+  sy_stage2<1, T>(sm, v, threadIdx.x, CW, ry);
+  fft_fwd<N, 1, false, T>(sm, v, r, c, tw);
+  const int ky = k1 + SY_R1 * ry;                    // the slot's column after stage 2
+  const double lc = ok ? lxy[kx + (long)Nxh * ky] : 1.0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int kz = pos_out<N, T>(r, c, q);
+    double f = -norm / (lc + lz[kz]);
+    if (kx == 0 && ky == 0 && kz == 0) f = 0.0;
+    v[q].x *= f;
+    v[q].y *= f;
+  }
+  fft_back<N, T>(sm, v, r, c, tw);
+  sy_stage2<-1, T>(sm, v, threadIdx.x, CW, ry);
+  if (ok) {
+#pragma unroll
+    for (int n1 = 0; n1 < 16; ++n1) col0[ncol * pos_in<N, T>(r, c, n1)] = v[n1];
+  }
+}
+
+// inverse x pass with the inverse of y stage 1: the workgroup of (ry, k) turns the kx x k1 block of T into the 32 real lines
+// j = ry + 8 n1 of level k of the compact (Nx, Ny, Nz) buffer.  Unnormalised (the z stage carries 1 / (Nx Ny Nz)).
+template <int N>
+__global__ void __launch_bounds__(2 * N) k_xinv_sy(const cd* __restrict__ spec, double* __restrict__ real, int Ny,
+                                                   const cd* __restrict__ tw) {
+  constexpr int T = 2 * N, M = N / 16, NH = N / 2 + 1, P = N / 2 + 8, LP = N + 16;
+  OCN_SHARED double sm[SMN * (T / 256)];
+  const int t = threadIdx.x;
+  const int rr = t % M, ln = t / M;
+  const int r = N == 512 ? rr & 15 : rr;
+  const int c = N == 512 ? ln + SY_R1 * (rr >> 4) : ln;
+  const int b = blockIdx.x;
+  const int ry = b % SY_R2, k = b / SY_R2;
+  cd* ls = (cd*)sm;
+  cd v[16];
+  // inverse y stage 1: x[p + 2 m] from Z[k1] = conj(W256^(ry k1)) T(k1); two threads per kx
+  const int p = t / NH, kx = t - p * NH;
+  if (p < 2) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      cd w0 = tw[(2 * ry * q) & 511], w1 = tw[(2 * ry * (q + 16)) & 511];
+      w0.y = -w0.y;
+      w1.y = -w1.y;
+      const cd z0 = cmul(spec[sy_at(P, kx, q, ry, k)], w0), z1 = cmul(spec[sy_at(P, kx, q + 16, ry, k)], w1);
+      v[q] = p ? csub(z0, z1) : cadd(z0, z1);
+    }
+    dft32_half<-1>(v, p, tw);
+#pragma unroll
+    for (int m = 0; m < 16; ++m) ls[(p + 2 * m) * NH + kx] = v[m];
+  }
+  __syncthreads();
+  // each line from its half spectrum: X[N - kx] = conj X[kx]
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) {
+    const int i = pos_in<N, T>(r, c, n1);
+    const cd z = ls[ln * NH + (i <= N / 2 ? i : N - i)];
+    v[n1] = i <= N / 2 ? z : cd{z.x, -z.y};
+  }
+  __syncthreads();
+  fft_fwd<N, -1, true, T, true>(sm, v, r, c, tw);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 16; ++q) sm[ln * LP + pos_out<N, T>(r, c, q)] = v[q].x;
+  __syncthreads();
+  double* out = real + (long)N * ((long)Ny * k + ry);
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    const int e = t + T * m;
+    const int l2 = e / N, i = e - l2 * N;
+    out[(long)N * SY_R2 * l2 + i] = sm[l2 * LP + i];
+  }
+}
+
 // host side ---------------------------------------------------------------------------------------------------
 struct ZSolve {
   cd* twmr = nullptr;      // exp(-2 pi i m / N), N = 320 or 384: the mixed-radix z stage (created on first use)
@@ -715,4 +959,46 @@ void zsolve_run(ocn_ctx* ctx, void* p, void* spec, int Nz, const double* lz, dou
   FFT_BY_N(Nz, ocn_launch_sync(k_zsolve<128>, g, b, s, a, z->ncol, (const double*)z->lxy, lz, tw, norm, zero_col),
            ocn_launch_sync(k_zsolve<256>, g, b, s, a, z->ncol, (const double*)z->lxy, lz, tw, norm, zero_col),
            ocn_launch_sync(k_zsolve<512>, g, b, s, a, z->ncol, (const double*)z->lxy, lz, tw, norm, zero_col))
+}
+
+// the three passes of the split-y form (see k_xfft_rhs_sy); `zs` holds lxy at pitch Nxh, `p` the twiddles
+void xfft_rhs_sy_run(ocn_model* m, void* p, void* spec, double dt) {
+  ZSolve* z = (ZSolve*)p;
+  const GridDev& g = m->gd;
+  const double* us = (m->fast_path ? m->us : pred_u(m)).interior();
+  const double* vs = (m->fast_path ? m->vs : pred_v(m)).interior();
+  const double* ws = (m->fast_path ? m->ws : pred_w(m)).interior();
+  dim3 gr((unsigned)(SY_R2 * g.Nz), 1, 1);
+  hipStream_t s = m->ctx->stream;
+  cd* sp = (cd*)spec;
+  const cd* tw = (const cd*)z->tw;
+  FFT_BY_N(g.Nx, ocn_launch_sync(k_xfft_rhs_sy<128>, gr, dim3(256, 1, 1), s, g, us, vs, ws, 1.0 / dt, 1, sp, tw),
+           ocn_launch_sync(k_xfft_rhs_sy<256>, gr, dim3(512, 1, 1), s, g, us, vs, ws, 1.0 / dt, 1, sp, tw),
+           ocn_launch_sync(k_xfft_rhs_sy<512>, gr, dim3(1024, 1, 1), s, g, us, vs, ws, 1.0 / dt, 1, sp, tw))
+}
+
+void zsolve_sy_run(ocn_ctx* ctx, void* p, void* spec, int Nx, int Nz, const double* lz, double norm) {
+  ZSolve* z = (ZSolve*)p;
+  const int Nxh = Nx / 2 + 1, P = split_y_pitch(Nx);
+  cd* a = (cd*)spec;
+  const cd* tw = (const cd*)z->tw;
+  const double* lxy = (const double*)z->lxy;
+  hipStream_t s = ctx->stream;
+  // 32 columns per workgroup (8 residues x 4 kx) at 128 and 256 levels, 16 (8 x 2) at 512.  256 levels in 256-thread workgroups
+  // (8 x 2 columns, three workgroups per CU) were slower at 256^3 (profiles/split_y_notes.md)
+  const unsigned t4 = (unsigned)(SY_R1 * ((Nxh + 3) / 4)), t2 = (unsigned)(SY_R1 * ((Nxh + 1) / 2));
+  FFT_BY_N(Nz, ocn_launch_sync(k_zsolve_sy<128, 256>, dim3(t4, 1, 1), dim3(256, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm),
+           ocn_launch_sync(k_zsolve_sy<256, 512>, dim3(t4, 1, 1), dim3(512, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm),
+           ocn_launch_sync(k_zsolve_sy<512, 512>, dim3(t2, 1, 1), dim3(512, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm))
+}
+
+void xinv_sy_run(ocn_ctx* ctx, void* p, const void* spec, double* real, int Nx, int Ny, int Nz) {
+  ZSolve* z = (ZSolve*)p;
+  dim3 gr((unsigned)(SY_R2 * Nz), 1, 1);
+  hipStream_t s = ctx->stream;
+  const cd* sp = (const cd*)spec;
+  const cd* tw = (const cd*)z->tw;
+  FFT_BY_N(Nx, ocn_launch_sync(k_xinv_sy<128>, gr, dim3(256, 1, 1), s, sp, real, Ny, tw),
+           ocn_launch_sync(k_xinv_sy<256>, gr, dim3(512, 1, 1), s, sp, real, Ny, tw),
+           ocn_launch_sync(k_xinv_sy<512>, gr, dim3(1024, 1, 1), s, sp, real, Ny, tw))
 }
