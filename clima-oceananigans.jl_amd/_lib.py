@@ -52,6 +52,10 @@ class SmagorinskyLillyDesc(C.Structure):
     _fields_ = [("C", C.c_double), ("Cb", C.c_double), ("Pr", C.c_double * MAX_TRACERS)]
 
 
+class ForcingDesc(C.Structure):
+    _fields_ = [("column_fields", C.c_uint32), ("field_fields", C.c_uint32)]
+
+
 class HydroDesc(C.Structure):
     _fields_ = [("free_surface", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("w", C.c_void_p), ("pHY", C.c_void_p),
                 ("ntracers", C.c_int32), ("tracers", C.POINTER(C.c_void_p)), ("Gn", C.POINTER(C.c_void_p)), ("Gm", C.POINTER(C.c_void_p)),
@@ -106,6 +110,10 @@ def load():
         "ocn_model_create_smagorinsky_lilly": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.POINTER(P)]),
         "ocn_model_create_with": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(P)]),
         "ocn_model_set_stokes_drift": (I, [P, I, PD, PD, PD, PD, PD, PD, I]),
+        "ocn_model_create_forced": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(ForcingDesc),
+                                        C.POINTER(P)]),
+        "ocn_model_set_forcing_column": (I, [P, I, I, PD, PD, PD, I]),
+        "ocn_model_set_forcing_field": (I, [P, I, PD, PD, PD, I, I, I]),
         "ocn_model_stage_times": (I, [P, D, C.POINTER(C.c_double * 3), C.POINTER(C.c_int32)]),
         "ocn_model_destroy": (None, [P]),
         "ocn_model_halo": (I, [P, C.POINTER(C.c_int32 * 3)]),

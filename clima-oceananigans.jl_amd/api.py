@@ -129,6 +129,122 @@ class UniformStokesDrift:
                                      ev(self.dt_us, zC), ev(self.dt_vs, zC)], dtype=np.float64)
 
 
+def _eval_nodes(f, shape, *args):
+    """``f(*args)`` on broadcast node arrays (point by point when ``f`` does not take arrays), as a float64 array of ``shape``"""
+    try:
+        out = np.broadcast_to(np.asarray(f(*args), dtype=np.float64), shape)
+    except Exception:
+        X, Y, Z = (np.broadcast_to(a, shape) for a in args[:3])
+        out = np.empty(shape, dtype=np.float64)
+        for idx in np.ndindex(*shape):
+            out[idx] = float(f(float(X[idx]), float(Y[idx]), float(Z[idx]), *args[3:]))
+    return np.array(out, dtype=np.float64)
+
+
+class GaussianMask:
+    """``GaussianMask{D}(center, width)``: ``exp(-(D - center)^2 / (2 width^2))`` (Forcings/relaxation.jl:116-138)."""
+
+    def __init__(self, direction, center=0.0, width=1.0):
+        if direction not in ("x", "y", "z"):
+            raise ValueError("GaussianMask: direction must be 'x', 'y' or 'z'")
+        self.direction, self.center, self.width = direction, float(center), float(width)
+
+    def __call__(self, x, y, z):
+        d = {"x": x, "y": y, "z": z}[self.direction]
+        return np.exp(-(d - self.center) ** 2 / (2 * self.width ** 2))
+
+
+class LinearTarget:
+    """``LinearTarget{D}(intercept, gradient)``: ``intercept + gradient * D`` (Forcings/relaxation.jl:160-178)."""
+
+    def __init__(self, direction, intercept=0.0, gradient=0.0):
+        if direction not in ("x", "y", "z"):
+            raise ValueError("LinearTarget: direction must be 'x', 'y' or 'z'")
+        self.direction, self.intercept, self.gradient = direction, float(intercept), float(gradient)
+
+    def __call__(self, x, y, z, t):
+        d = {"x": x, "y": y, "z": z}[self.direction]
+        return self.intercept + self.gradient * d
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+class Relaxation:
+    """``Relaxation(; rate, mask, target)`` (Forcings/relaxation.jl:1-84): ``rate * mask(x, y, z) * (target(x, y, z, t) - field)``.
+    ``mask``: ``None`` (one), a number, a ``GaussianMask`` or a function of ``(x, y, z)``; ``target``: ``None`` (zero), a number, a
+    ``LinearTarget`` or a function of ``(x, y, z, t)``.  Numbers and the ``"z"`` forms of the two classes make the column form
+    (tables of Nz numbers per stage, the target may depend on time); so do functions when ``uniform_in_xy=True`` declares that they
+    do not depend on x and y.  Everything else is the field form: (Nx, Ny, Nz) arrays evaluated once, constant in time."""
+
+    def __init__(self, rate, mask=None, target=None, uniform_in_xy=False):
+        if not _is_number(rate):
+            raise TypeError("Relaxation: rate must be a number")
+        for n, f in (("mask", mask), ("target", target)):
+            if f is not None and not _is_number(f) and not callable(f):
+                raise TypeError(f"Relaxation: {n} must be None, a number or a function")
+        self.rate, self.mask, self.target, self.uniform_in_xy = float(rate), mask, target, bool(uniform_in_xy)
+
+    def _part_is_column(self, f):
+        return f is None or _is_number(f) or (isinstance(f, (GaussianMask, LinearTarget)) and f.direction == "z") or self.uniform_in_xy
+
+    @property
+    def column(self):
+        return self._part_is_column(self.mask) and self._part_is_column(self.target)
+
+    def callables(self):
+        return [f for f in (self.mask, self.target) if callable(f) and not isinstance(f, (GaussianMask, LinearTarget))]
+
+    def sigma(self, X, Y, Z, shape):
+        if self.mask is None:
+            return np.full(shape, self.rate)
+        if _is_number(self.mask):
+            return np.full(shape, self.rate * float(self.mask))
+        return self.rate * _eval_nodes(self.mask, shape, X, Y, Z)        # (rate * mask) * (target - field): the reference's association
+
+    def tau(self, X, Y, Z, t, shape):
+        if self.target is None:
+            return np.zeros(shape)
+        if _is_number(self.target):
+            return np.full(shape, float(self.target))
+        return _eval_nodes(self.target, shape, X, Y, Z, float(t))
+
+
+class Forcing:
+    """``Forcing(func; parameters)`` (Forcings/forcing.jl, continuous_forcing.jl:116-125) without field dependencies:
+    ``func(x, y, z, t)`` or ``func(x, y, z, t, parameters)``.  Field form (evaluated once, must not depend on time) unless
+    ``uniform_in_xy=True`` declares that it depends on ``(z, t)`` only: then it is column form and is evaluated for every stage."""
+
+    def __init__(self, func, parameters=None, field_dependencies=None, discrete_form=False, uniform_in_xy=False):
+        if field_dependencies not in (None, (), []):
+            raise NotImplementedError("Forcing: field_dependencies are outside the path (the function would have to run on the device)")
+        if discrete_form:
+            raise NotImplementedError("Forcing: discrete_form=True is outside the path (the function would have to run on the device)")
+        if not callable(func):
+            raise TypeError("Forcing: func must be a function of (x, y, z, t[, parameters])")
+        self.func, self.parameters, self.uniform_in_xy = func, parameters, bool(uniform_in_xy)
+
+    @property
+    def column(self):
+        return self.uniform_in_xy
+
+    def callables(self):
+        return [self.func]
+
+    def values(self, X, Y, Z, t, shape):
+        if self.parameters is None:
+            return _eval_nodes(self.func, shape, X, Y, Z, float(t))
+        return _eval_nodes(self.func, shape, X, Y, Z, float(t), self.parameters)
+
+
+class AdvectiveForcing:
+    """``AdvectiveForcing`` of the reference (Forcings/advective_forcing.jl) is outside the path."""
+
+    def __init__(self, *a, **k):
+        raise NotImplementedError("AdvectiveForcing is outside the path (an advection operator with its own velocities)")
+
+
 class BuoyancyTracer:
     tracers = ("b",)
 
@@ -365,7 +481,8 @@ class NonhydrostaticModel:
     timestepper)`` (Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203)."""
 
     def __init__(self, grid, advection=None, buoyancy=None, coriolis=None, closure=None,
-                 boundary_conditions=None, tracers=(), timestepper="QuasiAdamsBashforth2", chi=0.1, stokes_drift=None):
+                 boundary_conditions=None, tracers=(), timestepper="QuasiAdamsBashforth2", chi=0.1, stokes_drift=None,
+                 forcing=None):
         self.grid, self.ctx, self.lib = grid, grid.ctx, grid.ctx.lib
         if stokes_drift is not None and not isinstance(stokes_drift, UniformStokesDrift):
             raise TypeError("stokes_drift must be a UniformStokesDrift or None")
@@ -459,7 +576,30 @@ class NonhydrostaticModel:
                 fill(d.bcs[names.index(fname)], side, bc)
         self.desc = d
         self.h = C.c_void_p()
-        if smag is None and stokes_drift is None:
+        # forcing: {field: one of Relaxation / Forcing / function of (x, y, z, t), or a tuple of them}
+        self.forcing = self._regularize_forcing(forcing, names)
+        self.forcing_uploads = 0           # column-table sets sent so far (one per stage slot whose contents changed)
+        self._forcing_sent = [None] * 3    # what each stage slot holds
+        if self.forcing:
+            fd = L.ForcingDesc()
+            for n, parts in self.forcing.items():
+                bit = 1 << names.index(n)
+                if parts["col_relax"] is not None or parts["col_F"]:
+                    fd.column_fields |= bit
+                if parts["fld_relax"] is not None or parts["fld_F"]:
+                    fd.field_fields |= bit
+            sd = None
+            if smag is not None:
+                sd = L.SmagorinskyLillyDesc()
+                sd.C, sd.Cb = smag.C, smag.Cb
+                for i, n in enumerate(self.tracer_names):
+                    if isinstance(smag.Pr, dict) and n not in smag.Pr:
+                        raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
+                    sd.Pr[i] = smag.Pr_of(n)
+            check(self.lib.ocn_model_create_forced(grid.h, C.byref(d), C.byref(sd) if sd is not None else None,
+                                                   L.FEATURE_STOKES_DRIFT if stokes_drift is not None else 0, C.byref(fd),
+                                                   C.byref(self.h)), self.ctx.h)
+        elif smag is None and stokes_drift is None:
             check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
         elif smag is None:
             check(self.lib.ocn_model_create_with(grid.h, C.byref(d), None, L.FEATURE_STOKES_DRIFT, C.byref(self.h)), self.ctx.h)
@@ -492,6 +632,8 @@ class NonhydrostaticModel:
             self.nu_e, self.kappa_e = FieldView(self, L.F_NU, "nu"), {}   # kappa_e = nu_e / Pr is an operation: no fields
         self.Gn = {n: FieldView(self, L.F_GN + i, n) for i, n in enumerate(names)}
         self.Gm = {n: FieldView(self, L.F_GM + i, n) for i, n in enumerate(names)}
+        if self.forcing:
+            self._forcing_check_and_upload_fields()
 
     def __del__(self):
         try:
@@ -528,11 +670,132 @@ class NonhydrostaticModel:
             t, _, stage = self.clock
             self._stokes_set(stage - 1, t)
 
+    # ---- forcing: host evaluation of Relaxation / Forcing into the library's column tables and field-form arrays ---------------
+    @staticmethod
+    def _regularize_forcing(forcing, names):
+        out = {}
+        for fname, spec in (forcing or {}).items():
+            if fname not in names:
+                raise ValueError(f"forcing for unknown field {fname}")
+            members = tuple(spec) if isinstance(spec, (tuple, list)) else (spec,)
+            parts = {"col_relax": None, "fld_relax": None, "col_F": [], "fld_F": []}
+            for mem in members:
+                if isinstance(mem, AdvectiveForcing):
+                    raise NotImplementedError("AdvectiveForcing is outside the path")
+                if callable(mem) and not isinstance(mem, (Relaxation, Forcing)):
+                    mem = Forcing(mem)                                   # a bare function of (x, y, z, t), as the reference wraps it
+                if isinstance(mem, Relaxation):
+                    key = "col_relax" if mem.column else "fld_relax"
+                    if parts[key] is not None:
+                        raise NotImplementedError(f"forcing of {fname}: more than one Relaxation in the "
+                                                  f"{'column' if mem.column else 'field'} form (two relaxations do not merge into one "
+                                                  "(sigma, tau) exactly)")
+                    parts[key] = mem
+                elif isinstance(mem, Forcing):
+                    parts["col_F" if mem.column else "fld_F"].append(mem)
+                else:
+                    raise TypeError(f"forcing of {fname}: {mem!r} is neither a Relaxation, a Forcing nor a function of (x, y, z, t)")
+            if members:
+                out[fname] = parts
+        return out
+
+    def _forcing_nodes(self, name):
+        g = self.grid
+        X, Y, Z = self.nodes(name)
+        return X[:g.Nx], Y[:, :g.Ny], Z[:, :, :g.Nz]
+
+    def _forcing_column_tables(self, name, t):
+        """(3, Nz): sigma, tau, F of the field's column form at time t"""
+        g, parts = self.grid, self.forcing[name]
+        X, Y, Z = self._forcing_nodes(name)
+        x0, y0, shape = X[:1], Y[:, :1], (1, 1, g.Nz)
+        tab = np.zeros((3, g.Nz))
+        r = parts["col_relax"]
+        if r is not None:
+            tab[0] = r.sigma(x0, y0, Z, shape).ravel()
+            tab[1] = r.tau(x0, y0, Z, t, shape).ravel()
+        for f in parts["col_F"]:                                         # tuple order
+            tab[2] += f.values(x0, y0, Z, t, shape).ravel()
+        return tab
+
+    def _forcing_check_and_upload_fields(self):
+        g = self.grid
+        t = self.time
+        t2 = t + 0.7384                                                  # the probe of time independence
+        for name, parts in self.forcing.items():
+            X, Y, Z = self._forcing_nodes(name)
+            # uniform_in_xy is a declaration: look at a second (x, y)
+            x1, y1 = X[:1] + 0.377 * g.Lx, Y[:, :1] + 0.291 * g.Ly
+            shape1 = (1, 1, g.Nz)
+            for mem in ([parts["col_relax"]] if parts["col_relax"] is not None else []) + parts["col_F"]:
+                if not mem.uniform_in_xy:
+                    continue
+                if isinstance(mem, Relaxation):
+                    a = (mem.sigma(X[:1], Y[:, :1], Z, shape1), mem.tau(X[:1], Y[:, :1], Z, t, shape1))
+                    b = (mem.sigma(x1, y1, Z, shape1), mem.tau(x1, y1, Z, t, shape1))
+                else:
+                    a, b = (mem.values(X[:1], Y[:, :1], Z, t, shape1),), (mem.values(x1, y1, Z, t, shape1),)
+                if not all(np.array_equal(p, q) for p, q in zip(a, b)):
+                    raise ValueError(f"forcing of {name}: declared uniform_in_xy=True but its values differ between two (x, y)")
+            shape = (g.Nx, g.Ny, g.Nz)
+            arrs = [None, None, None]
+            r = parts["fld_relax"]
+            if r is not None:
+                arrs[0], arrs[1] = r.sigma(X, Y, Z, shape), r.tau(X, Y, Z, t, shape)
+                if not np.array_equal(arrs[1], r.tau(X, Y, Z, t2, shape)):
+                    raise NotImplementedError(f"forcing of {name}: a Relaxation target that depends on x or y and on time is outside "
+                                              "the path (an (Nx, Ny, Nz) upload per stage)")
+                if r.target is None:
+                    arrs[1] = None
+            for f in parts["fld_F"]:
+                v = f.values(X, Y, Z, t, shape)
+                if not np.array_equal(v, f.values(X, Y, Z, t2, shape)):
+                    raise NotImplementedError(f"forcing of {name}: a Forcing that depends on x or y and on time is outside the path "
+                                              "(an (Nx, Ny, Nz) upload per stage); declare uniform_in_xy=True if it depends on (z, t) only")
+                arrs[2] = v if arrs[2] is None else arrs[2] + v
+            if r is not None or parts["fld_F"]:
+                self.set_forcing_field(name, *arrs)
+
+    def set_forcing_field(self, name, sigma=None, tau=None, F=None):
+        """replace the field-form arrays of ``name`` ((Nx, Ny, Nz) each; ``None``: absent).  Synchronises the model's stream."""
+        g = self.grid
+        names = ("u", "v", "w") + self.tracer_names
+        PD = C.POINTER(C.c_double)
+        keep = [None if a is None else np.asfortranarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (g.Nx, g.Ny, g.Nz)))
+                for a in (sigma, tau, F)]
+        ptr = [None if a is None else a.ctypes.data_as(PD) for a in keep]
+        check(self.lib.ocn_model_set_forcing_field(self.h, names.index(name), *ptr, g.Nx, g.Ny, g.Nz), self.ctx.h)
+
+    def _forcing_set(self, slot, t):
+        names = ("u", "v", "w") + self.tracer_names
+        cols = [n for n, p in self.forcing.items() if p["col_relax"] is not None or p["col_F"]]
+        if not cols:
+            return
+        tabs = {n: self._forcing_column_tables(n, t) for n in cols}
+        sent = self._forcing_sent[slot]
+        changed = [n for n in cols if sent is None or not np.array_equal(tabs[n], sent[n])]
+        if not changed:
+            return
+        PD = C.POINTER(C.c_double)
+        for n in changed:
+            tab = np.ascontiguousarray(tabs[n])
+            check(self.lib.ocn_model_set_forcing_column(self.h, names.index(n), slot, *[tab[i].ctypes.data_as(PD) for i in range(3)],
+                                                        self.grid.Nz), self.ctx.h)
+        self._forcing_sent[slot] = tabs
+        self.forcing_uploads += 1
+
+    def refresh_forcing(self):
+        """for the kernel-by-kernel verbs (``ocn_compute_tendencies`` ...): evaluate the column-form forcing at ``model.time`` into
+        the slot of the current stage.  ``time_step`` does this by itself for every stage of the step."""
+        if self.forcing:
+            t, _, stage = self.clock
+            self._forcing_set(stage - 1, t)
+
     @property
     def kernel_path(self):
         """which kernels serve this model and, when it is not the fastest set, why"""
-        buf = C.create_string_buffer(256)
-        check(self.lib.ocn_model_path(self.h, buf, 256), self.ctx.h)
+        buf = C.create_string_buffer(512)
+        check(self.lib.ocn_model_path(self.h, buf, 512), self.ctx.h)
         return buf.value.decode()
 
     @property
@@ -608,6 +871,9 @@ def time_step(model, dt, euler=False):
     if getattr(model, "stokes_drift", None) is not None:
         for slot, t in enumerate(model.stage_times(dt)):   # outside any graph capture; only slots whose tables changed are sent
             model._stokes_set(slot, t)
+    if getattr(model, "forcing", None):
+        for slot, t in enumerate(model.stage_times(dt)):
+            model._forcing_set(slot, t)
     check(model.lib.ocn_time_step(model.h, float(dt), int(bool(euler))), model.ctx.h)
 
 

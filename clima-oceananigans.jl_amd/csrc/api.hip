@@ -812,6 +812,9 @@ static uint64_t step_key(const ocn_model* m, double dt, int force_euler, std::ve
   fp(m->u); fp(m->v); fp(m->w); fp(m->us); fp(m->vs); fp(m->ws);
   for (int t = 0; t < m->nt; ++t) { fp(m->tr[t]); fp(m->trs[t]); }
   for (int f = 0; f < 3 + m->nt; ++f) { fp(m->Gn[f]); fp(m->Gm[f]); }
+  if (m->force_fld)   // field-form forcing arrays come and go with ocn_model_set_forcing_field
+    for (int f = 0; f < 3 + m->nt; ++f)
+      for (int t = 0; t < 3; ++t) words.push_back((uint64_t)(uintptr_t)m->force_arr[f][t]);
   uint64_t h = 1469598103934665603ull;
   for (uint64_t v : words) h = (h ^ v) * 1099511628211ull;
   return h;
@@ -876,9 +879,20 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null) and ocn_model_create_with share this body
-static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes, ocn_model** out) {
+// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with and ocn_model_create_forced share this body
+static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes,
+                        const ocn_forcing_desc* forcing, ocn_model** out) {
   ocn_ctx* ctx = g->ctx;
+  const uint32_t fcol = forcing ? forcing->column_fields : 0u, ffld = forcing ? forcing->field_fields : 0u;
+  if ((fcol | ffld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((fcol | ffld) >> (3 + desc->n_tracers)) != 0)) {
+    ocn_set_error(ctx, "ocn_model_create_forced: forcing masks 0x%x / 0x%x name fields beyond u, v, w and the model's %d tracers", fcol, ffld,
+                  desc->n_tracers);
+    return OCN_EINVAL;
+  }
+  if ((fcol | ffld) && (g->dist || g->dist_y || ctx->nranks > 1)) {
+    ocn_set_error(ctx, "forcing on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) is not supported");
+    return OCN_EUNSUPPORTED;
+  }
   if (stokes && g->topo[2] == OCN_FLAT) {
     ocn_set_error(ctx, "UniformStokesDrift on a grid with a Flat z is outside the path (its terms are vertical averages)");
     return OCN_EUNSUPPORTED;
@@ -1036,6 +1050,21 @@ static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smago
       return OCN_ENOMEM;
     }
   }
+  for (int f = 0; f < OCN_NF; ++f) m->force_ci[f] = -1;
+  if (fcol | ffld) {
+    m->force_col = fcol;
+    m->force_fld = ffld;
+    for (int f = 0; f < 3 + m->nt; ++f)   // u, v, w come as a block (internal.h force_col3): an undeclared one's tables stay zero
+      if ((fcol >> f & 1u) || (f < 3 && (fcol & 7u))) m->force_ci[f] = m->force_ncol++;
+    if (m->force_ncol) {
+      const size_t nb = (size_t)3 * m->force_ncol * 3 * g->N[2] * sizeof(double);
+      m->force_stage = (double*)calloc(1, nb);
+      if (!m->force_stage || hipMalloc((void**)&m->force_dev, nb) != hipSuccess || hipMemset(m->force_dev, 0, nb) != hipSuccess) {
+        ocn_model_destroy(m);
+        return OCN_ENOMEM;
+      }
+    }
+  }
   fused_read_knobs(m);
   m->fast_path = fused_available(m) ? 1 : 0;
   m->bz_fast = (!m->fast_path && fused_bz_available(m)) ? 1 : 0;
@@ -1074,7 +1103,7 @@ extern "C" {
 int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
   if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-  return model_create(g, desc, nullptr, false, out);
+  return model_create(g, desc, nullptr, false, nullptr, out);
 }
 
 int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
@@ -1082,7 +1111,13 @@ int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, 
 }
 
 int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features, ocn_model** out) {
+  return ocn_model_create_forced(g, desc, smag, features, nullptr, out);
+}
+
+int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
+  if (forcing && !(forcing->column_fields | forcing->field_fields)) forcing = nullptr;
   if (features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
     ocn_set_error(g->ctx, "ocn_model_create_with: unknown feature bits 0x%x", features);
     return OCN_EINVAL;
@@ -1090,7 +1125,7 @@ int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_sma
   const bool stokes = (features & OCN_FEATURE_STOKES_DRIFT) != 0;
   if (!smag) {
     if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-    return model_create(g, desc, nullptr, stokes, out);
+    return model_create(g, desc, nullptr, stokes, forcing, out);
   }
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
@@ -1123,7 +1158,7 @@ int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_sma
     ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
     return OCN_EINVAL;
   }
-  return model_create(g, desc, smag, stokes, out);
+  return model_create(g, desc, smag, stokes, forcing, out);
 }
 
 int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,
@@ -1156,6 +1191,85 @@ int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, c
   OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->stokes_dev + (size_t)stage * 6 * Nz, st, (size_t)6 * Nz * sizeof(double), hipMemcpyHostToDevice,
                                        m->ctx->stream));
   OCN_HIP_CHECK(m->ctx, hipEventRecord(m->stokes_ev[stage], m->ctx->stream));
+  return api_ret(m->ctx, OCN_OK);
+}
+
+static void host_scatter(const Field& f, const double* logical, const int lo[3], const int ext[3], std::vector<double>& phys);
+
+static int forcing_field_index(ocn_model* m, const char* who, int field) {
+  if (field < 0 || field >= 3 + m->nt) {
+    ocn_set_error(m->ctx, "%s: field %d is outside 0..%d (u, v, w, then the model's tracers)", who, field, 2 + m->nt);
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+
+int ocn_model_set_forcing_column(ocn_model* m, int field, int stage, const double* sigma, const double* tau, const double* F, int n) {
+  if (!m) return OCN_EINVAL;
+  if (int rc = forcing_field_index(m, "ocn_model_set_forcing_column", field)) return rc;
+  if (!(m->force_col >> field & 1u)) {
+    ocn_set_error(m->ctx, "ocn_model_set_forcing_column: field %d was not declared in ocn_forcing_desc.column_fields at creation", field);
+    return OCN_ESTATE;
+  }
+  if (stage < 0 || stage > 2) {
+    ocn_set_error(m->ctx, "ocn_model_set_forcing_column: stage %d is outside 0..2", stage);
+    return OCN_EINVAL;
+  }
+  const int Nz = m->gd.Nz;
+  if (n != Nz) {
+    ocn_set_error(m->ctx, "ocn_model_set_forcing_column: tables of %d entries on a grid of Nz = %d levels", n, Nz);
+    return OCN_EINVAL;
+  }
+  // library-owned staging, as ocn_model_set_stokes_drift: wait for this (slot, field)'s previous copy alone, never for the stream
+  const double* src[3] = {sigma, tau, F};
+  const size_t at = ((size_t)stage * m->force_ncol + m->force_ci[field]) * 3 * Nz;
+  double* st = m->force_stage + at;
+  hipEvent_t& ev = m->force_ev[stage][field];
+  if (ev) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(ev));
+  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&ev));
+  for (int t = 0; t < 3; ++t) {
+    if (src[t]) memcpy(st + (size_t)t * Nz, src[t], (size_t)Nz * sizeof(double));
+    else memset(st + (size_t)t * Nz, 0, (size_t)Nz * sizeof(double));
+  }
+  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->force_dev + at, st, (size_t)3 * Nz * sizeof(double), hipMemcpyHostToDevice, m->ctx->stream));
+  OCN_HIP_CHECK(m->ctx, hipEventRecord(ev, m->ctx->stream));
+  return api_ret(m->ctx, OCN_OK);
+}
+
+int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, const double* tau, const double* F, int nx, int ny, int nz) {
+  if (!m) return OCN_EINVAL;
+  if (int rc = forcing_field_index(m, "ocn_model_set_forcing_field", field)) return rc;
+  if (!(m->force_fld >> field & 1u)) {
+    ocn_set_error(m->ctx, "ocn_model_set_forcing_field: field %d was not declared in ocn_forcing_desc.field_fields at creation", field);
+    return OCN_ESTATE;
+  }
+  const int N[3] = {m->g->N[0], m->g->N[1], m->g->N[2]};
+  if (nx != N[0] || ny != N[1] || nz != N[2]) {
+    ocn_set_error(m->ctx, "ocn_model_set_forcing_field: arrays of (%d, %d, %d) on a grid of (Nx, Ny, Nz) = (%d, %d, %d)", nx, ny, nz, N[0], N[1], N[2]);
+    return OCN_EINVAL;
+  }
+  if (halo_settle(m)) return OCN_EHIP;
+  OCN_HIP_CHECK(m->ctx, hipStreamSynchronize(m->ctx->stream));   // no launch in flight reads the arrays being replaced
+  const Field& f = *model_field(m, field < 3 ? field : OCN_F_TRACER + field - 3);   // the layout the kernels' offsets address
+  const double* src[3] = {sigma, tau, F};
+  const int lo[3] = {m->g->H[0], m->g->H[1], m->g->H[2]};
+  std::vector<double> phys;
+  for (int t = 0; t < 3; ++t) {
+    double*& dev = m->force_arr[field][t];
+    if (!src[t]) {   // absent: the pointer is part of the step graphs' key, so graphs captured with the array are not replayed
+      if (dev) OCN_HIP_CHECK(m->ctx, hipFree(dev));
+      dev = nullptr;
+      continue;
+    }
+    if (!dev && hipMalloc((void**)&dev, f.n * sizeof(double)) != hipSuccess) {
+      dev = nullptr;
+      ocn_set_error(m->ctx, "ocn_model_set_forcing_field: out of device memory");
+      return OCN_ENOMEM;
+    }
+    phys.assign(f.n, 0.0);
+    host_scatter(f, src[t], lo, N, phys);
+    OCN_HIP_CHECK(m->ctx, hipMemcpy(dev, phys.data(), f.n * sizeof(double), hipMemcpyHostToDevice));
+  }
   return api_ret(m->ctx, OCN_OK);
 }
 
@@ -1211,6 +1325,14 @@ void ocn_model_destroy(ocn_model* m) {
   for (hipEvent_t e : m->stokes_ev)
     if (e) hipEventDestroy(e);
   free(m->stokes_stage);
+  hipFree(m->force_dev);
+  free(m->force_stage);
+  for (int f = 0; f < OCN_NF; ++f) {
+    for (int s = 0; s < 3; ++s) {
+      if (m->force_ev[s][f]) hipEventDestroy(m->force_ev[s][f]);
+      hipFree(m->force_arr[f][s]);
+    }
+  }
   hipFree(m->ypack_s);
   hipFree(m->ypack_r);
   poisson_destroy(m->solver);

@@ -530,6 +530,8 @@ struct RestArgs {
   double nu0;                           // added to nue: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
   int closure, coriolis, ntiles;
   const double* sk;                     // STOKES: the stage's UniformStokesDrift tables (internal.h stokes_slot)
+  const double* col3;                   // FORCE: the stage's column-form tables of u, v, w, nine runs of Nz doubles (internal.h force_col3) or null
+  ForceDev fo[3];                       // FORCE = 2: field-form forcing of u, v, w (internal.h force_of, parent bases; their col is unused)
 };
 
 // STOKES: UniformStokesDrift (StokesDrift.jl:66-80).  G_u, G_v of level k-1 need I_z(I_x w), I_z(I_y w) over faces k-1 and k; G_w of
@@ -538,7 +540,12 @@ struct RestArgs {
 // up / vp / wp -- in the reference's own association, I_z of I_x -- and start every segment from the parent arrays.  The east and
 // north values are read from the slab (never a lane shift): wave seams, the x wrap and the ghost row need no special case.  The
 // drift's shear and rate of change are per-level scalars of the stage's tables.
-template <int BX, int BY, bool ZB, bool NU0, bool STOKES = false>   // NU0: a.nu0 is added to the eddy viscosity
+// FORCE: sigma (tau - phi) + F of u, v, w with phi = uc, vc, wc of the slab: u and v enter with the other pointwise terms of level
+// k, w with hw.  1: the column form alone (a sponge layer) -- one table pointer, nine scalar loads at the absolute level k (segments
+// start in mid-column) issued at the top of the level, ahead of the stresses; 2: the field form as well, its values read at the
+// cell's own byte offset (stencils.h force_at_o).  The two are separate instantiations because the field form's nine array
+// pointers cost scalar registers that the column form alone does not need.
+template <int BX, int BY, bool ZB, bool NU0, bool STOKES = false, int FORCE = 0>   // NU0: a.nu0 is added to the eddy viscosity
 __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
   const double nu0 = NU0 ? a.nu0 : 0.0;
   constexpr int T = BX * BY, NR = BY + 1, SX = BX + 6;      // rows j0-1 .. j0+BY-1; columns -3 .. Nx+2 (the parent row)
@@ -612,6 +619,14 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
       __syncthreads();
       if (!last) dma(k + 1, kb ^ 1);
       const double* S = lds + kb * SLAB + ty * SX + tx;
+      double csu = 0, ctu = 0, cfu = 0, csv = 0, ctv = 0, cfv = 0, csw = 0, ctw = 0, cfw = 0;   // FORCE: column tables of level k
+      if (FORCE && !last && (FORCE == 1 || a.col3)) {
+        const double* t = a.col3 + k;
+        const int Nz = g.Nz;
+        csu = OCN_SLOAD(t); ctu = OCN_SLOAD(t + Nz); cfu = OCN_SLOAD(t + 2 * Nz);
+        csv = OCN_SLOAD(t + 3 * Nz); ctv = OCN_SLOAD(t + 4 * Nz); cfv = OCN_SLOAD(t + 5 * Nz);
+        csw = OCN_SLOAD(t + 6 * Nz); ctw = OCN_SLOAD(t + 7 * Nz); cfw = OCN_SLOAD(t + 8 * Nz);
+      }
       // hydrostatic pressure of this cell and its west / south neighbours (level k), issued early
       double p0 = 0, pw = 0, ps = 0;
       if (a.pH && full && !last) {
@@ -698,10 +713,20 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
             cu -= (p0 - pw) * rdx;
             cv -= (p0 - ps) * rdy;
           }
+          if (FORCE) {
+            cu += csu * (ctu - uc) + cfu;
+            cv += csv * (ctv - vc) + cfv;
+          }
+          if (FORCE == 2) {
+            if (force_any(a.fo[0])) cu += force_at_o(a.fo[0], k, g.Nz, c, uc);
+            if (force_any(a.fo[1])) cv += force_at_o(a.fo[1], k, g.Nz, c, vc);
+          }
           hu = cu + 2.0 * fma(xedge ? -t11 : e0 - t11, rdx, -t12 * rdy);
           hv = cv + 2.0 * fma(xedge ? -t12 : e1 - t12, rdx, -t22 * rdy);
           hw = 2.0 * fma(xedge ? -t13 : e2 - t13, rdx, -t23 * rdy);
           if (STOKES) hw -= 0.5 * (uxp + ux) * OCN_SLOAD(a.sk + 2 * g.Nz + k) + 0.5 * (vyp + vy) * OCN_SLOAD(a.sk + 3 * g.Nz + k);
+          if (FORCE) hw += csw * (ctw - wc) + cfw;
+          if (FORCE == 2 && force_any(a.fo[2])) hw += force_at_o(a.fo[2], k, g.Nz, c, wc);
           bu = t13;
           bv = t23;
           bw = t33;
@@ -873,12 +898,16 @@ struct Tracer3Args {
   int use_m, ntiles, zwrap;
   int rest_shell;   // REST: 1 = only the first and last level of G^n hold anything (boundary fluxes of a Bounded z; no walls in
                     // x / y): the other levels are neither zeroed by the caller nor read here
+  ForceDev fo;      // FORCE: the tracer's forcing (internal.h force_of, parent bases)
 };
 
 // KV: variable diffusivity (AnisotropicMinimumDissipation): -kappa_face dc/dn with kappa_face the two-point average of kappa_e
 // across the face (closure_kernel_operators.jl:43-48, 82-90) rides in the three face fluxes; kappa_e's slab sits in LDS next
 // to the tracer's, its value one level down in a register.
-template <int ADV, int BX, int BY, bool ZB, bool REST, bool IMG, int KV>   // KV 0: constant kappa; 1: kappa_e field; 2: kscale * field + kappa
+// FORCE (REST only): sigma (tau - c) + F of the tracer (stencils.h force_at_o) joins G of level k-1 before G^n is stored and the
+// update is formed, with c = zc[2], the slab's own value of that level -- on every level, whatever the rest_shell contract lets the
+// kernel skip of the incoming G^n.
+template <int ADV, int BX, int BY, bool ZB, bool REST, bool IMG, int KV, bool FORCE = false>   // KV 0: constant kappa; 1: kappa_e field; 2: kscale * field + kappa
 __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args a) {
   constexpr int T = BX * BY, NR = BY + 5, SX = BX + 6;
   constexpr int NG = (NR + BY - 1) / BY;
@@ -1026,7 +1055,8 @@ __global__ void __launch_bounds__(BX* BY) k_tracer_step3(GridDev g, Tracer3Args 
         if (k > k0) {
           const unsigned cm1 = c - szb;
           const double rzc = ZB ? g_rdzc(g, k - 1) : g.rdz;
-          const double G = rest - (own_h + (fb - own_b) * rzc);
+          double G = rest - (own_h + (fb - own_b) * rzc);
+          if (FORCE) G += force_at_o(a.fo, k - 1, g.Nz, cm1, zc[2]);
           sto(a.gn, cm1, G);
           const double inc = a.use_m ? a.dt * (a.cn * G + a.cm * gmv) : a.dt * a.cn * G;
           const double val = zc[2] + inc;
@@ -1077,6 +1107,7 @@ static bool fused_available_but_for_stokes(const ocn_model* m) {
 
 bool fused_available(const ocn_model* m) {
   if (m->stokes) return false;   // UniformStokesDrift: its terms live in k_rest4 / k_tend_uvw, like Coriolis
+  if (model_forced(m)) return false;   // forcing: its terms live in k_rest4 / k_tracer_step3<REST> / k_tend_uvw / k_tend_c
   return fused_available_but_for_stokes(m);
 }
 
@@ -1106,6 +1137,14 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
     const size_t l = strlen(buf);
     snprintf(buf + l, n - l, "; not the all-in-one periodic path: Stokes drift terms are served by %s",
              rest4_ok(m) ? "k_rest4" : "the general kernel");
+  }
+  if (model_forced(m)) {   // which kernels add sigma (tau - phi) + F, and whether forcing alone keeps the model off the all-in-one path
+    const size_t l = strlen(buf);
+    const bool mom = ((m->force_col | m->force_fld) & 7u) != 0, trc = ((m->force_col | m->force_fld) >> 3) != 0;
+    const bool tr3 = m->bz_fast && m->nt > 0 && fused_tracer3_ok(m);
+    snprintf(buf + l, n - l, "; %sforcing terms are served by %s%s%s", !m->stokes && fused_available_but_for_stokes(m) ? "not the all-in-one periodic path: " : "",
+             !mom ? "" : rest4_ok(m) ? "k_rest4" : "the general kernel (k_tend_uvw)", mom && trc ? " and " : "",
+             !trc ? "" : tr3 ? "k_tracer_step3 (REST)" : "the general kernel (k_tend_c)");
   }
   if (m->d.closure == OCN_CLOSURE_SMAG) {
     const size_t l = strlen(buf);
@@ -1378,6 +1417,13 @@ bool launch_rest4(ocn_model* m) {
   a.closure = m->d.closure;
   a.coriolis = m->d.coriolis_fplane;
   a.sk = stokes_slot(m);
+  a.col3 = force_col3(m);
+  int forced = a.col3 ? 1 : 0;         // the kernel's FORCE
+  for (int f = 0; f < 3; ++f) {
+    a.fo[f] = force_of(m, f, false);
+    a.fo[f].col = nullptr;             // the column form goes through col3
+    if (force_any(a.fo[f])) forced = 2;
+  }
   int bx = gd.Nx <= 64 ? 64 : gd.Nx <= 128 ? 128 : 256;
   int by = bx == 256 ? 4 : 8;
 #ifdef OCN_HOST_EMU
@@ -1397,7 +1443,8 @@ bool launch_rest4(ocn_model* m) {
   const dim3 blk(bx, by, 1), grd(nseg, 1, 1);
   hipStream_t s = m->ctx->stream;
   const bool zb = m->g->topo[2] == OCN_BOUNDED;
-#define REST4S(BXV, BYV, N0, SK) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0, SK>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0, SK>, grd, blk, s, gd, a); }
+#define REST4F(BXV, BYV, N0, SK, FO) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0, SK, FO>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0, SK, FO>, grd, blk, s, gd, a); }
+#define REST4S(BXV, BYV, N0, SK) { if (forced == 2) REST4F(BXV, BYV, N0, SK, 2) else if (forced) REST4F(BXV, BYV, N0, SK, 1) else REST4F(BXV, BYV, N0, SK, 0) }
 #define REST4N(BXV, BYV, N0) { if (a.sk) REST4S(BXV, BYV, N0, true) else REST4S(BXV, BYV, N0, false) }
 #define REST4(BXV, BYV) { if (a.nu0 != 0.0) REST4N(BXV, BYV, true) else REST4N(BXV, BYV, false) }
 #ifdef OCN_HOST_EMU
@@ -1407,6 +1454,7 @@ bool launch_rest4(ocn_model* m) {
 #undef REST4
 #undef REST4N
 #undef REST4S
+#undef REST4F
   return true;
 }
 
@@ -1512,31 +1560,35 @@ void launch_tracer3(ocn_model* m, double dt, double cn, double cm, int use_m, bo
     a.kappa = (m->d.closure == OCN_CLOSURE_SCALAR || smag) ? m->d.kappa[t] : 0.0;
     a.kap = smag ? m->nu_e.d : kv ? m->kappa_e[t].d : nullptr;
     a.kscale = smag ? m->smag_rPr[t] : 1.0;
+    a.fo = force_of(m, 3 + t, false);
+    const bool forced = rest && force_any(a.fo);   // forced models never take the all-in-one path (the IMG instantiations)
 #ifdef OCN_HOST_EMU
-#define TR3_EMU16(ADVV, ZBV, RESTV, IMGV) \
-    if (bx == 16) { if (kv == 2) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 2>, grd, blk, s, m->gd, a);  \
-                    else if (kv) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 1>, grd, blk, s, m->gd, a);   \
-                    else ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 0>, grd, blk, s, m->gd, a); } else
+#define TR3_EMU16(ADVV, ZBV, RESTV, IMGV, FOV) \
+    if (bx == 16) { if (kv == 2) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 2, FOV>, grd, blk, s, m->gd, a);  \
+                    else if (kv) ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 1, FOV>, grd, blk, s, m->gd, a);   \
+                    else ocn_launch_sync(k_tracer_step3<ADVV, 16, 4, ZBV, RESTV, IMGV, 0, FOV>, grd, blk, s, m->gd, a); } else
 #else
-#define TR3_EMU16(ADVV, ZBV, RESTV, IMGV)
+#define TR3_EMU16(ADVV, ZBV, RESTV, IMGV, FOV)
 #endif
-#define TR3_BX(ADVV, ZBV, RESTV, IMGV, KVV)                                                                      \
-    if (bx == 256) ocn_launch_sync(k_tracer_step3<ADVV, 256, 4, ZBV, RESTV, IMGV, KVV>, grd, blk, s, m->gd, a);     \
-    else if (bx == 128) ocn_launch_sync(k_tracer_step3<ADVV, 128, 8, ZBV, RESTV, IMGV, KVV>, grd, blk, s, m->gd, a); \
-    else ocn_launch_sync(k_tracer_step3<ADVV, 64, 8, ZBV, RESTV, IMGV, KVV>, grd, blk, s, m->gd, a);
-#define TR3_SHAPES(ADVV, ZBV, RESTV, IMGV)                                                                 \
-    TR3_EMU16(ADVV, ZBV, RESTV, IMGV)                                                                      \
-    if (kv == 2) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 2) } else if (kv) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 1) } else { TR3_BX(ADVV, ZBV, RESTV, IMGV, 0) }
+#define TR3_BX(ADVV, ZBV, RESTV, IMGV, KVV, FOV)                                                                      \
+    if (bx == 256) ocn_launch_sync(k_tracer_step3<ADVV, 256, 4, ZBV, RESTV, IMGV, KVV, FOV>, grd, blk, s, m->gd, a);     \
+    else if (bx == 128) ocn_launch_sync(k_tracer_step3<ADVV, 128, 8, ZBV, RESTV, IMGV, KVV, FOV>, grd, blk, s, m->gd, a); \
+    else ocn_launch_sync(k_tracer_step3<ADVV, 64, 8, ZBV, RESTV, IMGV, KVV, FOV>, grd, blk, s, m->gd, a);
+#define TR3_SHAPES(ADVV, ZBV, RESTV, IMGV, FOV)                                                                 \
+    TR3_EMU16(ADVV, ZBV, RESTV, IMGV, FOV)                                                                      \
+    if (kv == 2) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 2, FOV) } else if (kv) { TR3_BX(ADVV, ZBV, RESTV, IMGV, 1, FOV) } else { TR3_BX(ADVV, ZBV, RESTV, IMGV, 0, FOV) }
+#define TR3_REST(ADVV, ZBV) { if (forced) { TR3_SHAPES(ADVV, ZBV, true, false, true) } else { TR3_SHAPES(ADVV, ZBV, true, false, false) } }
 #define TR3_MODE(ADVV)                                 \
-    if (!rest) { TR3_SHAPES(ADVV, false, false, true) } \
-    else if (zb) { TR3_SHAPES(ADVV, true, true, false) } \
-    else { TR3_SHAPES(ADVV, false, true, false) }
+    if (!rest) { TR3_SHAPES(ADVV, false, false, true, false) } \
+    else if (zb) TR3_REST(ADVV, true)                   \
+    else TR3_REST(ADVV, false)
     switch (m->d.advection) {
       case ADV_WENO_Z: TR3_MODE(ADV_WENO_Z) break;
       case ADV_WENO_JS: TR3_MODE(ADV_WENO_JS) break;
       default: TR3_MODE(ADV_U5) break;
     }
 #undef TR3_MODE
+#undef TR3_REST
 #undef TR3_SHAPES
 #undef TR3_BX
   }

@@ -163,6 +163,18 @@ struct ocn_model {
   double* stokes_dev = nullptr;  // [3][6][Nz]
   double* stokes_stage = nullptr;   // host staging of the same shape (the source of the asynchronous uploads)
   hipEvent_t stokes_ev[3] = {nullptr, nullptr, nullptr};   // recorded behind each slot's upload
+  // Forcing (ocn_model_create_forced): G_phi += sigma (tau - phi) + F for the fields of the two masks (bit f: u, v, w, tracers).
+  // Column form: force_dev holds, per stage slot and declared field (force_ci[f]: its rank among them), sigma, tau, F as three runs
+  // of Nz doubles; device addresses never change, so a captured step graph reads the current contents.  Field form: up to three
+  // arrays per field in the layout of that field's parent array (the tiled kernels read them at the cell's own byte offset, the
+  // general kernels at its interior index); an absent array is a null pointer and its load is skipped.  The pointers are part of
+  // the step graphs' key.
+  uint32_t force_col = 0, force_fld = 0;
+  int force_ncol = 0, force_ci[OCN_NF];
+  double* force_dev = nullptr;      // [3][force_ncol][3][Nz]
+  double* force_stage = nullptr;    // host staging of the same shape
+  hipEvent_t force_ev[3][OCN_NF] = {};   // recorded behind each (slot, field) upload
+  double* force_arr[OCN_NF][3] = {};     // field form: sigma, tau, F
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
 };
@@ -176,6 +188,28 @@ inline bool pnhs_lazy(const ocn_model* m) { return m->fast_path && !m->g->dist &
 // the Stokes-drift tables a tendency launch reads: the slot of the current stage (null: no Stokes drift)
 inline const double* stokes_slot(const ocn_model* m) {
   return m->stokes ? m->stokes_dev + (size_t)(m->stage - 1) * 6 * m->gd.Nz : nullptr;
+}
+
+// the column tables of u, v, w of the current stage, nine runs of Nz doubles (k_rest4): when one of the three is declared all three
+// have tables -- they are the first three of a slot -- and an undeclared one's stay zero.  Null: none of them is declared.
+inline const double* force_col3(const ocn_model* m) {
+  return (m->force_col & 7u) ? m->force_dev + (size_t)(m->stage - 1) * m->force_ncol * 3 * m->gd.Nz : nullptr;
+}
+inline bool model_forced(const ocn_model* m) { return (m->force_col | m->force_fld) != 0; }
+// what a tendency launch reads for field f (0, 1, 2: u, v, w; 3 + t: tracer t): the column tables of the current stage and the
+// field-form arrays, as parent bases (tiled kernels) or moved to the first interior cell (general kernels)
+inline ForceDev force_of(const ocn_model* m, int f, bool interior) {
+  ForceDev fo = {nullptr, nullptr, nullptr, nullptr};
+  if (m->force_col >> f & 1u)
+    fo.col = m->force_dev + ((size_t)(m->stage - 1) * m->force_ncol + m->force_ci[f]) * 3 * m->gd.Nz;
+  if (m->force_fld >> f & 1u) {
+    const Field& F = f == 0 ? m->u : f == 1 ? m->v : f == 2 ? m->w : m->tr[f - 3];
+    const size_t org = interior ? (size_t)(F.interior() - F.d) : 0;
+    fo.fs = m->force_arr[f][0] ? m->force_arr[f][0] + org : nullptr;
+    fo.ft = m->force_arr[f][1] ? m->force_arr[f][1] + org : nullptr;
+    fo.ff = m->force_arr[f][2] ? m->force_arr[f][2] + org : nullptr;
+  }
+  return fo;
 }
 
 Field* model_field(ocn_model* m, int id);

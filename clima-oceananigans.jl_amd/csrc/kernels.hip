@@ -23,6 +23,7 @@ struct Phys {
   const double* nu_e;   // AMD, SmagorinskyLilly
   double nu0;           // added to nu_e: the ScalarDiffusivity of a (SmagorinskyLilly, ScalarDiffusivity) tuple, else 0
   const double* sk;     // UniformStokesDrift tables of this stage (internal.h stokes_slot) or null
+  ForceDev fo[3];       // forcing of u, v, w (internal.h force_of, interior pointers); all null: none
   int buoyancy, bi, Ti, Si;
   double g, alpha, beta;
 };
@@ -51,7 +52,8 @@ OCN_DEVFN double nu_cff(const Phys& ph, long p, long sy, long sz) {
   return ph.nu_e ? 0.25 * ((ph.nu_e[p - sy - sz] + ph.nu_e[p - sz]) + (ph.nu_e[p - sy] + ph.nu_e[p])) + ph.nu0 : ph.nu;
 }
 
-template <int ADV, bool WALLS>
+// FORCE: the model has forcing on u, v or w (ph.fo); the instantiations of unforced models never look at it
+template <int ADV, bool WALLS, bool FORCE = false>
 __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, const double* __restrict__ v,
                            const double* __restrict__ w, double* __restrict__ Gu, double* __restrict__ Gv,
                            double* __restrict__ Gw) {
@@ -133,6 +135,12 @@ __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, con
     gw -= 0.5 * (0.5 * (u[c - sz] + u[c + 1 - sz]) + 0.5 * (u[c] + u[c + 1])) * OCN_SLOAD(sk + 2 * Nz) +
           0.5 * (0.5 * (v[c - sz] + v[c + sy - sz]) + 0.5 * (v[c] + v[c + sy])) * OCN_SLOAD(sk + 3 * Nz);
   }
+  // ---- forcing (nonhydrostatic_tendency_kernel_functions.jl:71,128,180): sigma (tau - phi) + F at the field's own nodes ----
+  if (FORCE) {
+    if (force_any(ph.fo[0])) gu += force_at(ph.fo[0], k, Nz, c, u[c]);
+    if (force_any(ph.fo[1])) gv += force_at(ph.fo[1], k, Nz, c, v[c]);
+    if (force_any(ph.fo[2])) gw += force_at(ph.fo[2], k, Nz, c, w[c]);
+  }
   // ---- viscous stress divergence (closure_kernel_operators.jl:22-41; fluxes -2 nu Sigma) ----
   if (ph.closure != OCN_CLOSURE_NONE) {
     auto rzf = [&](int kf) { return zf ? 0.0 : g_rdzf(g, kf); };
@@ -162,10 +170,10 @@ __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, con
   Gw[c] = gw;
 }
 
-template <int ADV, bool WALLS>
+template <int ADV, bool WALLS, bool FORCE = false>   // FORCE: the tracer has forcing (fo)
 __global__ void k_tend_c(GridDev g, const double* __restrict__ u, const double* __restrict__ v,
                          const double* __restrict__ w, const double* __restrict__ q, double kap,
-                         const double* __restrict__ kap_e, double ks, int closure, double* __restrict__ Gc) {
+                         const double* __restrict__ kap_e, double ks, int closure, ForceDev fo, double* __restrict__ Gc) {
   int i, j;
   ocn_cell_ij(i, j);
   const int k = blockIdx.z;   // one level per workgroup: k is wave-uniform, so spacings are scalar loads and 1/dz is computed once per wave
@@ -199,6 +207,7 @@ __global__ void k_tend_c(GridDev g, const double* __restrict__ u, const double* 
       d += (kz(c + sz) * (q[c + sz] - q[c]) / g_dzf(g, k + 1) - kz(c) * (q[c] - q[c - sz]) / g_dzf(g, k)) * rdzc;
     gc += d;
   }
+  if (FORCE) gc += force_at(fo, k, g.Nz, c, q[c]);   // forcing (nonhydrostatic_tendency_kernel_functions.jl:231)
   Gc[c] = gc;
 }
 
@@ -259,18 +268,23 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
   const bool smag = m->d.closure == OCN_CLOSURE_SMAG;
   ph.nu0 = smag ? m->d.nu : 0.0;
   ph.sk = stokes_slot(m);
+  for (int f = 0; f < 3; ++f) ph.fo[f] = force_of(m, f, true);
+  const bool forced_uvw = force_any(ph.fo[0]) || force_any(ph.fo[1]) || force_any(ph.fo[2]);
   static const dim3 b = tuned_block("OCNHIP_TEND_BLOCK", dim3(64, 4, 1));
   const dim3 gr = grid3(g, b);
   const double *u = m->u.interior(), *v = m->v.interior(), *w = m->w.interior();
   double *Gu = m->Gn[0].interior(), *Gv = m->Gn[1].interior(), *Gw = m->Gn[2].interior();
-#define TEND_TRACER(A, W, t)                                                                               \
-  ocn_launch(k_tend_c<A, W>, gr, b, s, g, u, v, w, (const double*)m->tr[t].interior(),                    \
+#define TEND_TRACER_F(A, W, t, FO)                                                                         \
+  ocn_launch(k_tend_c<A, W, FO>, gr, b, s, g, u, v, w, (const double*)m->tr[t].interior(),                \
              (smag || m->d.closure == OCN_CLOSURE_SCALAR) ? m->d.kappa[t] : 0.0,                          \
              (const double*)(smag ? m->nu_e.interior() : m->kappa_e[t].present ? m->kappa_e[t].interior() : nullptr), \
-             smag ? m->smag_rPr[t] : 1.0, m->d.closure, m->Gn[3 + t].interior());
+             smag ? m->smag_rPr[t] : 1.0, m->d.closure, force_of(m, 3 + t, true), m->Gn[3 + t].interior());
+#define TEND_TRACER(A, W, t) if (force_any(force_of(m, 3 + t, true))) { TEND_TRACER_F(A, W, t, true) } else { TEND_TRACER_F(A, W, t, false) }
+#define TEND_UVW(A, W) { if (forced_uvw) ocn_launch(k_tend_uvw<A, W, true>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); \
+                         else ocn_launch(k_tend_uvw<A, W, false>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); }
 #define TEND_LAUNCH(A, W)                                                       \
-  if (skip_momentum_advection) { if (!launch_rest4(m)) ocn_launch(k_tend_uvw<ADV_NONE, W>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); }  \
-  else ocn_launch(k_tend_uvw<A, W>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw);      \
+  if (skip_momentum_advection) { if (!launch_rest4(m)) TEND_UVW(ADV_NONE, W) }  \
+  else TEND_UVW(A, W)                                                           \
   for (int t = 0; t < m->nt; ++t) {                                             \
     if (skip_tracer_advection) { tracer_gn_clear(m, t); }  /* advection AND closure flux come from the tiled tracer kernel; boundary fluxes are added below */ \
     else { TEND_TRACER(A, W, t) }                                               \
@@ -296,6 +310,8 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
 #undef TEND_CASE
 #undef TEND_LAUNCH
 #undef TEND_TRACER
+#undef TEND_TRACER_F
+#undef TEND_UVW
   // boundary contributions in every Bounded direction
   for (int dim = 0; dim < 3; ++dim) {
     if (m->g->topo[dim] != OCN_BOUNDED) continue;

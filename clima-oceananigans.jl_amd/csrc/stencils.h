@@ -250,3 +250,29 @@ OCN_DEVFN double recon_o(const double* b, unsigned o, unsigned s, double ut) {
   double A3 = pos ? m3 : c2, A2 = pos ? m2 : c1, A1 = pos ? m1 : c0, A0 = pos ? c0 : m1, B1 = pos ? c1 : m2;
   return recon5<ADV>(A3, A2, A1, A0, B1, pos);
 }
+
+// ---- forcing of one field (Forcings/relaxation.jl:80-84, continuous_forcing.jl:116-125): G += sigma (tau - phi) + F -------------
+// sigma = rate * mask formed on the host: (rate * mask) * (target - field) is the reference's own association.
+struct ForceDev {
+  const double* col;            // column form: sigma, tau, F of the stage at the field's z nodes, three runs of Nz doubles (null: none)
+  const double *fs, *ft, *ff;   // field form: sigma, tau, F in the fields' layout (null: absent; tau is read next to a sigma only)
+};
+__host__ __device__ inline bool force_any(const ForceDev& fo) { return fo.col || fo.fs || fo.ff; }
+// the column form at level k (wave-uniform: three scalar loads, no vector memory traffic)
+OCN_DEVFN double force_col(const double* col, int k, int Nz, double phi) {
+  return OCN_SLOAD(col + k) * (OCN_SLOAD(col + Nz + k) - phi) + OCN_SLOAD(col + 2 * Nz + k);
+}
+// general kernels: interior pointers, element index c
+OCN_DEVFN double force_at(const ForceDev& fo, int k, int Nz, long c, double phi) {
+  double r = fo.col ? force_col(fo.col, k, Nz, phi) : 0.0;
+  if (fo.fs) r += fo.fs[c] * ((fo.ft ? fo.ft[c] : 0.0) - phi);
+  if (fo.ff) r += fo.ff[c];
+  return r;
+}
+// tiled kernels: parent bases, byte offset of the cell
+OCN_DEVFN double force_at_o(const ForceDev& fo, int k, int Nz, unsigned boff, double phi) {
+  double r = fo.col ? force_col(fo.col, k, Nz, phi) : 0.0;
+  if (fo.fs) r += ldo(fo.fs, boff) * ((fo.ft ? ldo(fo.ft, boff) : 0.0) - phi);
+  if (fo.ff) r += ldo(fo.ff, boff);
+  return r;
+}

@@ -126,9 +126,11 @@ typedef struct ocn_bc {
 } ocn_bc;
 
 /* NonhydrostaticModel(; grid, advection, buoyancy, coriolis, closure, boundary_conditions, tracers,
- * timestepper) -- Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203.  Forcings, Stokes drift,
- * background fields, immersed boundaries and particles are user Julia closures / out of scope: not
- * representable across a C ABI, the shim rejects them. */
+ * timestepper) -- Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203.  A UniformStokesDrift and forcings without field
+ * dependencies (Relaxation, ContinuousForcing) are user functions that the caller evaluates into tables and arrays
+ * (ocn_model_create_with, ocn_model_create_forced).  Forcings with field dependencies, discrete-form and advective forcings,
+ * background fields, immersed boundaries and particles are user Julia closures / out of scope: not representable across a C
+ * ABI, the shim rejects them. */
 typedef struct ocn_model_desc {
   int32_t advection;   /* OCN_ADV_*                                   */
   int32_t stepper;     /* OCN_STEPPER_*                               */
@@ -206,6 +208,38 @@ int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, c
 /* clock.time at which each stage of the next ocn_time_step(m, dt, .) computes its tendencies, accumulated exactly as the
  * steppers do (runge_kutta_3.jl:81-152: the clock ticks between stages): *nstages = 1 (AB2) or 3 (RK3). */
 int ocn_model_stage_times(const ocn_model* m, double dt, double times[3], int32_t* nstages);
+/* NonhydrostaticModel(; forcing = (u = Relaxation(...), T = (Relaxation(...), Forcing(func)), ...)) -- Forcings/relaxation.jl:80-84,
+ * continuous_forcing.jl:116-125, multiple_forcings.jl, nonhydrostatic_tendency_kernel_functions.jl:71,128,180,231.  For every
+ * forced field phi, at phi's own nodes -- u (Face, Center, Center), v (Center, Face, Center), w (Center, Center, Face k = 1..Nz),
+ * tracers at centres -- and with t = clock.time of the stage:
+ *     G_phi += sigma (tau - phi) + F
+ * sigma = rate * mask(x, y, z) (the caller forms the product), tau = target(x, y, z, t) or a number, F = the sum of the field's
+ * ContinuousForcings without field dependencies.  The functions cannot cross this boundary; the caller evaluates them, in one or
+ * both of two forms per field:
+ *   column form -- sigma, tau, F depend on (z, t): three tables of Nz doubles per field and stage slot, read as wave-uniform
+ *     scalars; they may change every stage (ocn_model_set_forcing_column);
+ *   field form  -- three (Nx, Ny, Nz) arrays per field, constant in time (ocn_model_set_forcing_field).
+ * Bit f of either mask stands for field f: 0, 1, 2 are u, v, w and 3 + t is tracer t.  Forcing is a creation-time property: it
+ * decides the kernels (never the all-in-one periodic path; ocn_model_path says so) and allocates the storage whose device
+ * addresses never change.  Everything is zero until set.  desc == NULL or both masks zero: exactly ocn_model_create_with.
+ * OCN_EINVAL: a bit beyond the model's fields; OCN_EUNSUPPORTED: a distributed grid (z- or y-slabs, more than one rank,
+ * OCNHIP_FORCE_DIST).  Flat directions are allowed. */
+typedef struct ocn_forcing_desc {
+  uint32_t column_fields, field_fields;
+} ocn_forcing_desc;
+int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, ocn_model** out);
+/* Column-form tables of `field` for the tendency evaluation of stage `stage` (0..2; QuasiAdamsBashforth2 uses 0; the
+ * kernel-by-kernel verbs read slot `stage of ocn_clock` - 1): sigma, tau, F at the field's z nodes k = 1..Nz, n = Nz entries
+ * each; a NULL table is all zeros.  The values are copied before the call returns and uploaded on the model's stream; the device
+ * addresses of a slot never change, so a replayed step graph reads whatever was set last.  OCN_ESTATE: the field was not declared
+ * in column_fields; OCN_EINVAL: field or stage out of range, n != Nz. */
+int ocn_model_set_forcing_column(ocn_model* m, int field, int stage, const double* sigma, const double* tau, const double* F, int n);
+/* Field-form arrays of `field`: sigma, tau, F at the field's nodes i = 1..Nx, j = 1..Ny, k = 1..Nz, column-major (Nx, Ny, Nz); a
+ * NULL array is absent (zero: the kernels skip its load; tau is only read next to a sigma).  Synchronises the model's stream,
+ * then replaces the arrays; callable between steps.  OCN_ESTATE: the field was not declared in field_fields; OCN_EINVAL: field
+ * out of range, (nx, ny, nz) != (Nx, Ny, Nz). */
+int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, const double* tau, const double* F, int nx, int ny, int nz);
 void ocn_model_destroy(ocn_model* m);
 /* which kernels serve this model, and if not the fastest ones, why (e.g. "general kernels: parent arrays of 2 GiB or
  * more exceed the tiled kernels' 32-bit byte offsets").  Writes at most n bytes incl. the terminating 0. */

@@ -92,7 +92,8 @@ function bc_of(bc, keep)
 end
 
 function ocn_model(arch::ROCmGPU, gridh, m)                                             # m: the fields NonhydrostaticModel(...) assembled
-    isempty(m.forcing) && isempty(m.background_fields) || error("forcings and background fields are Julia closures: outside the C ABI")
+    isempty(m.background_fields) || error("background fields are Julia closures: outside the C ABI")
+    fplan = forcing_plan(m)                                                             # refuses what cannot be tabulated, by name
     m.stokes_drift === nothing || m.stokes_drift isa UniformStokesDrift || error("stokes_drift: only UniformStokesDrift is on the path")
     names = keys(m.tracers); nt = length(names)
     pad(t) = ntuple(i -> i <= length(t) ? Float64(t[i]) : 0.0, MAXTR)
@@ -122,7 +123,12 @@ function ocn_model(arch::ROCmGPU, gridh, m)                                     
                      closure == 2 ? sides(m.diffusivity_fields.νₑ) : none,
                      ntuple(i -> (closure == 2 && i <= nt) ? sides(m.diffusivity_fields.κₑ[i]) : none, MAXTR))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if m.stokes_drift === nothing
+    if fplan.column_fields | fplan.field_fields != 0   # forcing is a creation-time property too: ocn_forcing_desc { column_fields, field_fields }
+        fd = UInt32[fplan.column_fields, fplan.field_fields]
+        GC.@preserve keep fd check(ccall((:ocn_model_create_forced, libocnhip), Cint,
+                                         (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ptr{UInt32}, Ref{Ptr{Cvoid}}),
+                                         gridh, desc, C_NULL, UInt32(m.stokes_drift === nothing ? 0 : 1), fd, h), arch.ctx)
+    elseif m.stokes_drift === nothing
         GC.@preserve keep check(ccall((:ocn_model_create, libocnhip), Cint, (Ptr{Cvoid}, Ref{ModelDesc}, Ref{Ptr{Cvoid}}), gridh, desc, h), arch.ctx)
     else  # a creation-time property: it decides the kernels.  OCN_FEATURE_STOKES_DRIFT = 1; a SmagorinskyLilly desc goes where C_NULL is
         GC.@preserve keep check(ccall((:ocn_model_create_with, libocnhip), Cint, (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ref{Ptr{Cvoid}}),
@@ -189,9 +195,91 @@ end
 # the kernel-by-kernel verbs read the slot of the current stage: set_stokes_drift!(model, model.clock.stage - 1, model.clock.time, sent)
 # before calculate_tendencies!(model)
 
+# forcing = (u = Relaxation(...), T = (Relaxation(...), Forcing(func)), ...) (Forcings/relaxation.jl:80-84, continuous_forcing.jl:116-125,
+# multiple_forcings.jl): G_phi += sigma (tau - phi) + F at phi's own nodes.  Accepted: Relaxation, ContinuousForcing without field
+# dependencies, and tuples (MultipleForcings) of them; refused by name: field dependencies, DiscreteForcing, AdvectiveForcing, a second
+# Relaxation of the same form on one field.  The functions stay in Julia and are evaluated on the nodes: numbers, GaussianMask{:z},
+# LinearTarget{:z} and the default mask / target make the column form (three tables of Nz numbers per field and stage, at the clock
+# times of ocn_model_stage_times, re-sent only when they changed); everything else the field form ((Nx, Ny, Nz) arrays, evaluated
+# once; a probe at a second time must agree).  Not run: no Julia toolchain exists where this was written.
+using Oceananigans.Forcings: ContinuousForcing, DiscreteForcing, MultipleForcings, AdvectiveForcing, Relaxation, GaussianMask, LinearTarget
+forcing_members(f) = f isa MultipleForcings ? f.forcings : (f,)
+is_relaxation(f) = f isa ContinuousForcing && f.func isa Relaxation
+column_part(p) = p isa Number || p isa GaussianMask{:z} || p isa LinearTarget{:z} || p === Oceananigans.Forcings.onefunction ||
+                 p === Oceananigans.Forcings.zerofunction
+column_member(f) = is_relaxation(f) && column_part(f.func.mask) && column_part(f.func.target)
+function forcing_plan(m)
+    names = (:u, :v, :w, keys(m.tracers)...)
+    plan = (column_fields = UInt32(0), field_fields = UInt32(0), members = Dict{Symbol, Any}())
+    col, fld = UInt32(0), UInt32(0)
+    for (i, n) in enumerate(names)
+        haskey(m.forcing, n) || continue
+        mem = [f for f in forcing_members(m.forcing[n]) if f !== Oceananigans.Forcings.zeroforcing && !(f isa Returns)]
+        isempty(mem) && continue
+        for f in mem
+            f isa AdvectiveForcing && error("forcing of $n: AdvectiveForcing is outside the path")
+            f isa DiscreteForcing && error("forcing of $n: discrete_form = true is outside the path")
+            f isa ContinuousForcing || error("forcing of $n: $(typeof(f)) is outside the path")
+            is_relaxation(f) || isempty(f.field_dependencies) || error("forcing of $n: field_dependencies are outside the path")
+        end
+        count(column_member, mem) <= 1 && count(f -> is_relaxation(f) && !column_member(f), mem) <= 1 ||
+            error("forcing of $n: more than one Relaxation of the same form (two relaxations do not merge into one (sigma, tau) exactly)")
+        any(column_member, mem) && (col |= UInt32(1) << (i - 1))
+        any(!column_member, mem) && (fld |= UInt32(1) << (i - 1))
+        plan.members[n] = (i - 1, mem)
+    end
+    return (column_fields = col, field_fields = fld, members = plan.members)
+end
+field_nodes(model, n) = (loc = n == :u ? (Face(), Center(), Center()) : n == :v ? (Center(), Face(), Center()) :
+                               n == :w ? (Center(), Center(), Face()) : (Center(), Center(), Center());
+                         g = model.grid; ([xnode(loc[1], i, g) for i in 1:g.Nx], [ynode(loc[2], j, g) for j in 1:g.Ny], [znode(loc[3], k, g) for k in 1:g.Nz]))
+target_at(r, x, y, z, t) = r.target isa Number ? Float64(r.target) : Float64(r.target(x, y, z, t))
+function set_forcing_columns!(model::RM, slot, t, sent)       # model.auxiliary_fields.forcing_plan / forcing_sent = Any[nothing, nothing, nothing]
+    Nz = model.grid.Nz; tabs = Dict{Symbol, Any}()
+    for (n, (f, mem)) in model.auxiliary_fields.forcing_plan.members
+        any(column_member, mem) || continue
+        x, y, z = field_nodes(model, n); r = first(filter(column_member, mem)).func
+        tabs[n] = (Float64[r.rate * r.mask(x[1], y[1], zk) for zk in z], Float64[target_at(r, x[1], y[1], zk, t) for zk in z], zeros(Nz))
+    end
+    for (n, tab) in tabs
+        sent[slot + 1] !== nothing && get(sent[slot + 1], n, nothing) == tab && continue
+        check(ccall((:ocn_model_set_forcing_column, libocnhip), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint),
+                    handle(model), model.auxiliary_fields.forcing_plan.members[n][1], slot, tab..., Nz), model.architecture.ctx)
+    end
+    sent[slot + 1] = tabs
+    return nothing
+end
+function set_forcing_fields!(model::RM)                        # once, after construction: the field form is constant in time
+    g = model.grid; t = model.clock.time
+    for (n, (f, mem)) in model.auxiliary_fields.forcing_plan.members
+        rest = filter(!column_member, mem); isempty(rest) && continue
+        x, y, z = field_nodes(model, n)
+        ev(fun) = Float64[fun(x[i], y[j], z[k]) for i in 1:g.Nx, j in 1:g.Ny, k in 1:g.Nz]
+        rel = filter(is_relaxation, rest); fs = filter(!is_relaxation, rest)
+        value(c, tt) = (X, Y, Z) -> c.parameters === nothing ? c.func(X, Y, Z, tt) : c.func(X, Y, Z, tt, c.parameters)
+        σ = isempty(rel) ? nothing : ev((X, Y, Z) -> rel[1].func.rate * rel[1].func.mask(X, Y, Z))
+        τ = isempty(rel) ? nothing : ev((X, Y, Z) -> target_at(rel[1].func, X, Y, Z, t))
+        F = isempty(fs) ? nothing : sum(ev(value(c, t)) for c in fs)
+        (isempty(rel) || τ == ev((X, Y, Z) -> target_at(rel[1].func, X, Y, Z, t + 0.7384))) && (isempty(fs) || F == sum(ev(value(c, t + 0.7384)) for c in fs)) ||
+            error("forcing of $n: a forcing that depends on x or y and on time is outside the path (an (Nx, Ny, Nz) upload per stage)")
+        ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+        GC.@preserve σ τ F check(ccall((:ocn_model_set_forcing_field, libocnhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint),
+                                       handle(model), f, ptr(σ), ptr(τ), ptr(F), g.Nx, g.Ny, g.Nz), model.architecture.ctx)
+    end
+end
+function refresh_forcing!(model::RM, Δt)            # before ocn_time_step, like refresh_stokes_drift!
+    isempty(model.auxiliary_fields.forcing_plan.members) && return nothing
+    times = zeros(3); n = Ref(Int32(0))
+    check(ccall((:ocn_model_stage_times, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ref{Int32}), handle(model), Δt, times, n))
+    for s in 1:n[]
+        set_forcing_columns!(model, s - 1, times[s], model.auxiliary_fields.forcing_sent)
+    end
+end
+
 # TimeSteppers/quasi_adams_bashforth_2.jl:70-104 and runge_kutta_3.jl:81-152 -- preferred, coarsest overload
 function time_step!(model::RM, Δt; euler=false)
     refresh_stokes_drift!(model, Δt)
+    refresh_forcing!(model, Δt)
     check(ccall((:ocn_time_step, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Cint), handle(model), Δt, euler), model.architecture.ctx)
     # clock mirrors ocn_clock (TimeSteppers/clock.jl:48-60)
     t = Ref(0.0); it = Ref(Int64(0)); st = Ref(Int32(0))
