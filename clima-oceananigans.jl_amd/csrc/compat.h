@@ -22,6 +22,8 @@
 #include <hipfft/hipfft.h>
 
 #define OCN_DEVFN __device__ __forceinline__
+// waves per SIMD the kernel is compiled for: lo = hi = n caps its registers at 512 / n (next to __launch_bounds__)
+#define OCN_WAVES_PER_EU(...) __attribute__((amdgpu_waves_per_eu(__VA_ARGS__)))
 
 // g_ocn_dry: a time step is being REPLAYED from a hipGraph (api.hip): the host-side bookkeeping of the step runs again
 // (clock, buffer rotations), every launch and stream operation is skipped
@@ -59,6 +61,9 @@ static inline void ocn_launch_impl(const char* what, K kern, dim3 grid, dim3 blo
 // an opaque use of three loaded values: the compiler must have them in registers at this point of every path (it places
 // the s_waitcnt of their loads here instead of wherever their registers are next written)
 #define OCN_TOUCH3(a, b, c) asm volatile("" ::"v"(a), "v"(b), "v"(c))
+// a 32-bit value the compiler must take as new from here on: what it computed from the old one (addresses, table entries it
+// loaded through them) is not kept in registers for a second use far away but formed again there
+#define OCN_FORGET(x) asm volatile("" : "+v"(x))
 
 // ---- wave-level primitives of the tiled kernels ----------------------------------------------------------------------
 // 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4: no VGPR round trip): lane l of the
@@ -128,11 +133,13 @@ extern std::recursive_mutex g_emu_launch_mutex;   // one emulated kernel at a ti
 #define __host__
 #define __forceinline__ inline
 #define __launch_bounds__(...)
+#define OCN_WAVES_PER_EU(...)
 #define OCN_DEVFN inline
 #define OCN_SHARED static
 #define OCN_SCHED_FENCE() ((void)0)
 #define OCN_ASYNC(call) ((void)(call))
 #define OCN_TOUCH3(a, b, c) ((void)0)
+#define OCN_FORGET(x) ((void)0)
 
 typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorOutOfMemory = 2 };

@@ -171,6 +171,37 @@ template <int T = 256> OCN_DEVFN void fft512_partner(double* sm, const cd* v, cd
   __syncthreads();
 }
 
+// the radix-2 decimation step of N = 512 from the thread's 16 points v and its partner's p, and its inverse (which fetches the
+// partner's points itself: barriers inside)
+template <int S, int T = 256> OCN_DEVFN void fft512_dif(cd* v, const cd* p, int r, int c, const cd* tw) {
+  const int h = (c / FftGeo<512, T>::C) & 1;
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) {
+    if (h == 0) v[n1] = cadd(v[n1], p[n1]);                      // x[n] + x[n + 256]
+    else {
+      cd w = tw[(r + 16 * n1) & 511];                            // W512^n, n = r + 16 n1
+      if (S < 0) w.y = -w.y;
+      v[n1] = cmul(csub(p[n1], v[n1]), w);                       // (x[n] - x[n + 256]) W^n: own = x[n + 256]
+    }
+  }
+}
+template <int T = 256> OCN_DEVFN void fft512_undif(double* sm, cd* v, int r, int c, const cd* tw) {
+  // u0 = x[n] + x[n+256], u1 = (x[n] - x[n+256]) W^n  ->  2 x[n] = u0 + u1 conj(W^n), ...
+  const int h = (c / FftGeo<512, T>::C) & 1;
+  if (h == 1) {
+#pragma unroll
+    for (int n1 = 0; n1 < 16; ++n1) {
+      cd w = tw[(r + 16 * n1) & 511];
+      w.y = -w.y;
+      v[n1] = cmul(v[n1], w);
+    }
+  }
+  cd p[16];
+  fft512_partner<T>(sm, v, p, r, c);
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) v[n1] = h == 0 ? cadd(v[n1], p[n1]) : csub(p[n1], v[n1]);     // 2 x[n], 2 x[n + 256]
+}
+
 // forward / backward N-point transform of the team's points.  In: v[n1] = x[r + M' n1 (+ 256 h)] with M' = 8 (N = 128)
 // or 16; out: see the table above.  Unnormalised; S = +1: exp(-i ...), S = -1: exp(+i ...).
 // XLANE: the x pass -- real input, and its thread layout puts the partner 16 lanes away in the same wave: the partner's
@@ -195,16 +226,7 @@ template <int N, int S, bool XLANE = false, int T = 256, bool CPLX = false> OCN_
 #pragma unroll
       for (int q = 0; q < 16; ++q) p[q] = cd{ocn_shfl_xor16(v[q].x), 0.0};
     } else fft512_partner<T>(sm, v, p, r, c);
-    const int h = (c / FftGeo<512, T>::C) & 1;
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) {
-      if (h == 0) v[n1] = cadd(v[n1], p[n1]);                    // x[n] + x[n + 256]
-      else {
-        cd w = tw[(r + 16 * n1) & 511];                          // W512^n, n = r + 16 n1
-        if (S < 0) w.y = -w.y;
-        v[n1] = cmul(csub(p[n1], v[n1]), w);                     // (x[n] - x[n + 256]) W^n: own = x[n + 256]
-      }
-    }
+    fft512_dif<S, T>(v, p, r, c, tw);
   }
   dft16<S>(v);
   fft_stage2<N, S, XLANE, T>(sm, v, r, c, tw);
@@ -263,22 +285,7 @@ template <int N, int T = 256> OCN_DEVFN void fft_back(double* sm, cd* v, int r, 
 #pragma unroll
   for (int q = 0; q < 16; ++q) v[q].y = sm[ri(q)];
   dft16<-1>(v);                                                  // r = n2 again: v[n1] = u_h[r + 16 n1]
-  if (N == 512) {
-    // undo the decimation step: u0 = x[n] + x[n+256], u1 = (x[n] - x[n+256]) W^n  ->  2 x[n] = u0 + u1 conj(W^n), ...
-    const int h = (c / FftGeo<512, T>::C) & 1;
-    if (h == 1) {
-#pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) {
-        cd w = tw[(r + 16 * n1) & 511];
-        w.y = -w.y;
-        v[n1] = cmul(v[n1], w);
-      }
-    }
-    cd p[16];
-    fft512_partner<T>(sm, v, p, r, c);
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) v[n1] = h == 0 ? cadd(v[n1], p[n1]) : csub(p[n1], v[n1]);   // 2 x[n], 2 x[n + 256]
-  }
+  if (N == 512) fft512_undif<T>(sm, v, r, c, tw);
 }
 
 // thread -> (r, column slot c, element index of v[q] along the transformed direction) for data whose COLUMNS are adjacent
@@ -699,72 +706,146 @@ __global__ void __launch_bounds__(2 * N) k_xfft_rhs_sy(GridDev g, const double* 
   }
 }
 
-// y stage 2 (S = +1) or its inverse inside the z pass.  In: the thread of residue slot ry holds v[n1] of column T(kx; k1, ry); the 8
-// threads of a (kx, r) swap so that slot a holds points n1 = 2 a, 2 a + 1 of all 8 residues, transform them, and swap back:
-// out: slot s holds v[n1] of column ky = k1 + 32 s.  The 8 threads are lanes of one wave (t = kxs + CW slot + ...), so only the
-// first and the last barrier are the workgroup's.
-template <int S, int T> OCN_DEVFN void sy_stage2(double* sm, cd* v, int t, int cw, int ry) {
-  constexpr int ST = T + 2;                          // level pitch of the image: the 8 x CW readers of a level pair hit different banks
-  const int t0 = t - cw * ry;                        // the thread of slot 0
-  const int lv = 2 * ry;
-  cd u[16];                                          // u[8 e + q]: point 2 a + e of residue q
-  __syncthreads();
+// ---- z stage of the split-y form: y stage 2 sits BETWEEN the two stages of the z transform ---------------------------------------
+// y stage 2 acts on the residue ry, the z transform on the level, and the z twiddle W^(n2 k1z) does not depend on ry: they commute.
+// So z stage 1 (dft16 over n1, twiddle) runs first, per residue, in the layout the loads deliver (A); ONE exchange takes the data to
+// layout B, where slot a of a (kx, n2) holds k1z = 2 a, 2 a + 1 of all 8 residues and runs two dft8 over them; ONE exchange takes it
+// from there to the z stage 2 layout (C): thread r' = k1z of slot s holds n2 = 0..15 of column ky = k1 + 32 s (N = 128: k1z = r' and
+// r' + 8, n2 = 0..7 each).  Backwards the mirror image: four exchanges in all, where transforming y first and swapping back took six.
+// All three layouts share one LDS image, element (k1z, n2, column slot c) at k1z PI + n2 CS + c:
+//   A  thread t = c + CS n2 writes its own v[k1z] at k1z PI + t;
+//   B  slot a reads, and later writes, (2 a + e) PI + t0 + CW q for e = 0, 1 and q = 0..7 (t0: the thread of slot 0): the SAME 16
+//      places for residue q on one side and ky slot q on the other, and no other thread of layout B touches them;
+//   C  thread (r', c) reads r' PI + n2 CS + c.
+// A <-> B stays inside a wave (the 8 slots are lanes t0 + CW q of one wave); B <-> C crosses the workgroup.  The pitch PI = T + CW / 2
+// puts the 8 slots x CW kx of a half wave on 32 different banks (2 PI = CW mod 32) and leaves the reads of layout C, 32 consecutive c,
+// conflict-free.
+template <int N, int T> struct SyGeo {
+  static constexpr int CW = FftGeo<N, T>::C / SY_R2;   // consecutive kx of a workgroup
+  static constexpr int PI = T + CW / 2;
+  static constexpr int SM = 16 * PI;                   // doubles of LDS
+  // 256 levels (the 256^3 step): two workgroups of 8 waves per CU, so that one loads or stores while the other computes: 128 VGPRs.
+  // 128 levels: three 4-wave workgroups per CU as before (four, which the registers would allow, measured 43 us against 40 at
+  // 256 x 256 x 128: 1032 workgroups on 1024 places).  512 levels: 128 VGPRs spill (the partner's 16 points): one workgroup per CU.
+  static constexpr int WLO = N == 256 ? 4 : N == 128 ? 3 : 1, WHI = N == 256 ? 4 : N == 128 ? 3 : 8;
+};
+
+// S = +1: A -> B, dft8 over the residues, B -> C.  S = -1: C -> B, inverse dft8, B -> A.  v is source and target of every exchange.
+template <int N, int S, int T> OCN_DEVFN void sy_exchange(double* sm, cd* v, int t, int r, int c, int ry) {
+  typedef FftGeo<N, T> G;
+  constexpr int CW = SyGeo<N, T>::CW, PI = SyGeo<N, T>::PI;
+  const int g0 = 2 * ry * PI + t - CW * ry;
+  auto own = [&](int k) { return k * PI + t; };
+  auto grp = [&](int q) { return g0 + (q >> 3) * PI + CW * (q & 7); };
+  auto col = [&](int q) { return N == 128 ? (r + 8 * (q >> 3)) * PI + (q & 7) * G::CS + c : r * PI + q * G::CS + c; };
+  if (S > 0) {
+    // nothing has used the image yet (N = 512: fft512_partner ends with a barrier)
 #pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) sm[n1 * ST + t] = v[n1].x;
-  OCN_WAVE_SYNC();
+    for (int k = 0; k < 16; ++k) sm[own(k)] = v[k].x;
+    OCN_WAVE_SYNC();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) u[q].x = sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)];
-  OCN_WAVE_SYNC();
+    for (int q = 0; q < 16; ++q) v[q].x = sm[grp(q)];
+    OCN_WAVE_SYNC();
 #pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) sm[n1 * ST + t] = v[n1].y;
-  OCN_WAVE_SYNC();
+    for (int k = 0; k < 16; ++k) sm[own(k)] = v[k].y;
+    OCN_WAVE_SYNC();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) u[q].y = sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)];
-  dft8<S>(u);
-  dft8<S>(u + 8);
-  OCN_WAVE_SYNC();
+    for (int q = 0; q < 16; ++q) v[q].y = sm[grp(q)];
+    dft8<S>(v);
+    dft8<S>(v + 8);
 #pragma unroll
-  for (int q = 0; q < 16; ++q) sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)] = u[q].x;
-  OCN_WAVE_SYNC();
+    for (int q = 0; q < 16; ++q) sm[grp(q)] = v[q].x;           // the places this thread alone has just read
+    __syncthreads();
 #pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) v[n1].x = sm[n1 * ST + t];
-  OCN_WAVE_SYNC();
+    for (int q = 0; q < 16; ++q) v[q].x = sm[col(q)];
+    __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 16; ++q) sm[(lv + (q >> 3)) * ST + t0 + cw * (q & 7)] = u[q].y;
-  OCN_WAVE_SYNC();
+    for (int q = 0; q < 16; ++q) sm[grp(q)] = v[q].y;
+    __syncthreads();
 #pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) v[n1].y = sm[n1 * ST + t];
-  __syncthreads();
+    for (int q = 0; q < 16; ++q) v[q].y = sm[col(q)];
+  } else {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sm[col(q)] = v[q].x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q].x = sm[grp(q)];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sm[col(q)] = v[q].y;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q].y = sm[grp(q)];
+    dft8<S>(v);
+    dft8<S>(v + 8);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sm[grp(q)] = v[q].x;
+    OCN_WAVE_SYNC();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k].x = sm[own(k)];
+    OCN_WAVE_SYNC();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sm[grp(q)] = v[q].y;
+    OCN_WAVE_SYNC();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k].y = sm[own(k)];
+  }
 }
 
-// z stage with y stage 2 in front of and behind it.  One workgroup = 8 residues x CW consecutive kx of one k1, all N levels.
-// lxy[kx + Nxh ky] as in k_zsolve; the zeroed mode is kx = ky = kz = 0.
+// workgroups of the z stage: Nx / (2 CW) tiles of CW consecutive kx < Nx / 2 for each of the 32 k1, then the Nyquist column
+// kx = Nx / 2 of CW consecutive k1 per workgroup (one kx slot each): every slot of every workgroup owns a column
+__host__ __device__ inline int sy_zblocks(int Nxh, int CW) { return SY_R1 * ((Nxh - 1) / CW) + SY_R1 / CW; }
+
+// One workgroup = 8 residues x CW columns (kx, k1), all N levels.  lxy[kx + Nxh ky] as in k_zsolve; the zeroed mode is
+// kx = ky = kz = 0.
 template <int N, int T>
-__global__ void __launch_bounds__(T) k_zsolve_sy(cd* __restrict__ a, int Nxh, int P, const double* __restrict__ lxy,
-                                                 const double* __restrict__ lz, const cd* __restrict__ tw, double norm) {
+__global__ void __launch_bounds__(T) OCN_WAVES_PER_EU(SyGeo<N, T>::WLO, SyGeo<N, T>::WHI)
+    k_zsolve_sy(cd* __restrict__ a, int Nxh, int P, const double* __restrict__ lxy, const double* __restrict__ lz,
+                const cd* __restrict__ tw, double norm) {
   typedef FftGeo<N, T> G;
-  constexpr int CW = G::C / SY_R2;
-  static_assert(G::CS <= 64 && 16 * (T + 2) <= SMN * (T / 256), "the residues of a column group must be lanes of one wave");
-  OCN_SHARED double sm[SMN * (T / 256)];
+  typedef SyGeo<N, T> Y;
+  constexpr int CW = Y::CW;
+  constexpr int TS = 512 / (N == 512 ? 256 : N);     // table stride of the roots of the 16 x M network
+  static_assert(G::CS <= 64, "the residues of a column group must be lanes of one wave");
+  static_assert(T * 16 <= Y::SM, "the image also serves fft512_partner");
+  static_assert(Y::SM * sizeof(double) <= OCN_LDS_BYTES / 2, "k_zsolve_sy: two workgroups must fit the LDS of a CU");
+  OCN_SHARED double sm[Y::SM];
   int r, c, col;
   team_of<N, T>(threadIdx.x, r, c, col);
   const int kxs = col % CW, ry = col / CW;
-  const int tiles = (Nxh + CW - 1) / CW;            // the padding of a row (kx >= Nxh) gets no workgroup
-  // neighbouring kx tiles share 128-byte lines: handed out XCD-major as in k_yfft
-  const int nblk = SY_R1 * tiles;
-  const int b = ((int)blockIdx.x % 8) * (nblk / 8) + (int)blockIdx.x / 8;
-  const int tile = b % tiles, k1 = b / tiles;
-  const int kx = tile * CW + kxs;
-  const bool ok = kx < Nxh;
-  const long ncol = (long)P * SY_R1 * SY_R2;
-  cd* col0 = a + sy_at(P, kx, k1, ry, 0);
+  const int tf = (Nxh - 1) / CW, nfull = SY_R1 * tf, nn = SY_R1 / CW;
+  // The Nyquist workgroups (16-byte runs, the slowest) come first, one or two per XCD (nn = 8 or 16).  The full ones follow:
+  // neighbouring kx tiles share 128-byte lines, so they are handed out XCD-major as in k_yfft (nfull is a multiple of 8, and
+  // of 2: the two tiles of a line are neighbours in the order of their XCD).  With the Nyquist workgroups last the pass took
+  // 90 us at 256^3 instead of 75 (profiles/zsolve_sy_order_notes.md).
+  const bool nyq = (int)blockIdx.x < nn;
+  const int bi = (int)blockIdx.x - nn;
+  const int b = nyq ? (int)blockIdx.x : (bi % 8) * (nfull / 8) + bi / 8;
+  const int kx = nyq ? Nxh - 1 : (b % tf) * CW + kxs;
+  const int k1 = nyq ? b * CW + kxs : b / tf;
+  // the thread's 16 levels: the byte offset of the first (32 bits: under 0.3 GiB at every size served) and a uniform step
+  unsigned o0 = (unsigned)(sy_at(P, kx, k1, ry, pos_in<N, T>(r, c, 0)) * (long)sizeof(cd));
+  const unsigned step = (unsigned)((long)P * SY_R1 * SY_R2 * (N == 128 ? 8 : 16) * (long)sizeof(cd));
+  auto at = [&](int n1) { return (cd*)((char*)a + (size_t)step * n1 + o0); };   // a uniform base and the thread's offset
   cd v[16];
 #pragma unroll
-  for (int n1 = 0; n1 < 16; ++n1) v[n1] = ok ? col0[ncol * pos_in<N, T>(r, c, n1)] : cd{0, 0};
-  sy_stage2<1, T>(sm, v, threadIdx.x, CW, ry);
-  fft_fwd<N, 1, false, T>(sm, v, r, c, tw);
-  const int ky = k1 + SY_R1 * ry;                    // the slot's column after stage 2
-  const double lc = ok ? lxy[kx + (long)Nxh * ky] : 1.0;
+  for (int n1 = 0; n1 < 16; ++n1) v[n1] = *at(n1);
+  if (N == 512) {
+    cd p[16];
+    fft512_partner<T>(sm, v, p, r, c);
+    fft512_dif<1, T>(v, p, r, c, tw);
+  }
+  dft16<1>(v);                                       // z stage 1: v[k1z] = Z[k1z][n2 = r] of residue ry
+#pragma unroll
+  for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], tw[((r * k) * TS) & 511]);
+  sy_exchange<N, 1, T>(sm, v, threadIdx.x, r, c, ry);
+  if (N == 128) {
+    dft8<1>(v);
+    dft8<1>(v + 8);
+  } else dft16<1>(v);
+  const int ky = k1 + SY_R1 * ry;                    // the slot's column after y stage 2
+  const double lc = lxy[kx + (long)Nxh * ky];
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const int kz = pos_out<N, T>(r, c, q);
@@ -773,12 +854,24 @@ __global__ void __launch_bounds__(T) k_zsolve_sy(cd* __restrict__ a, int Nxh, in
     v[q].x *= f;
     v[q].y *= f;
   }
-  fft_back<N, T>(sm, v, r, c, tw);
-  sy_stage2<-1, T>(sm, v, threadIdx.x, CW, ry);
-  if (ok) {
+  if (N == 128) {
+    dft8<-1>(v);
+    dft8<-1>(v + 8);                                 // v[n2 + 8 h] = Z[k1z = r + 8 h][n2]
+  } else dft16<-1>(v);                               // v[n2] = Z[k1z = r][n2]
+  int rb = r;
+  OCN_FORGET(rb);                                    // the roots are loaded again here, not held in 60 registers since stage 1
 #pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) col0[ncol * pos_in<N, T>(r, c, n1)] = v[n1];
+  for (int q = 1; q < 16; ++q) {
+    cd w = tw[((N == 128 ? (rb + 8 * (q >> 3)) * (q & 7) : rb * q) * TS) & 511];
+    w.y = -w.y;
+    v[q] = cmul(v[q], w);
   }
+  sy_exchange<N, -1, T>(sm, v, threadIdx.x, r, c, ry);
+  dft16<-1>(v);                                      // v[n1] = x[r + M' n1] of residue ry again (N = 512: of its half)
+  if (N == 512) fft512_undif<T>(sm, v, r, c, tw);
+  OCN_FORGET(o0);                                    // nor the 16 addresses
+#pragma unroll
+  for (int n1 = 0; n1 < 16; ++n1) *at(n1) = v[n1];
 }
 
 // inverse x pass with the inverse of y stage 1: the workgroup of (ry, k) turns the kx x k1 block of T into the 32 real lines
@@ -986,7 +1079,7 @@ void zsolve_sy_run(ocn_ctx* ctx, void* p, void* spec, int Nx, int Nz, const doub
   hipStream_t s = ctx->stream;
   // 32 columns per workgroup (8 residues x 4 kx) at 128 and 256 levels, 16 (8 x 2) at 512.  256 levels in 256-thread workgroups
   // (8 x 2 columns, three workgroups per CU) were slower at 256^3 (profiles/split_y_notes.md)
-  const unsigned t4 = (unsigned)(SY_R1 * ((Nxh + 3) / 4)), t2 = (unsigned)(SY_R1 * ((Nxh + 1) / 2));
+  const unsigned t4 = (unsigned)sy_zblocks(Nxh, 4), t2 = (unsigned)sy_zblocks(Nxh, 2);
   FFT_BY_N(Nz, ocn_launch_sync(k_zsolve_sy<128, 256>, dim3(t4, 1, 1), dim3(256, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm),
            ocn_launch_sync(k_zsolve_sy<256, 512>, dim3(t4, 1, 1), dim3(512, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm),
            ocn_launch_sync(k_zsolve_sy<512, 512>, dim3(t2, 1, 1), dim3(512, 1, 1), s, a, Nxh, P, lxy, lz, tw, norm))
