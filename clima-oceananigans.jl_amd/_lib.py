@@ -56,6 +56,10 @@ class ForcingDesc(C.Structure):
     _fields_ = [("column_fields", C.c_uint32), ("field_fields", C.c_uint32)]
 
 
+class BackgroundDesc(C.Structure):
+    _fields_ = [("column_members", C.c_uint32), ("field_members", C.c_uint32)]
+
+
 class HydroDesc(C.Structure):
     _fields_ = [("free_surface", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("w", C.c_void_p), ("pHY", C.c_void_p),
                 ("ntracers", C.c_int32), ("tracers", C.POINTER(C.c_void_p)), ("Gn", C.POINTER(C.c_void_p)), ("Gm", C.POINTER(C.c_void_p)),
@@ -114,6 +118,10 @@ def load():
                                         C.POINTER(P)]),
         "ocn_model_set_forcing_column": (I, [P, I, I, PD, PD, PD, I]),
         "ocn_model_set_forcing_field": (I, [P, I, PD, PD, PD, I, I, I]),
+        "ocn_model_create_background": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(ForcingDesc),
+                                            C.POINTER(BackgroundDesc), C.POINTER(P)]),
+        "ocn_model_set_background_column": (I, [P, I, I, PD, I]),
+        "ocn_model_set_background_field": (I, [P, I, PD, I, I, I]),
         "ocn_model_stage_times": (I, [P, D, C.POINTER(C.c_double * 3), C.POINTER(C.c_int32)]),
         "ocn_model_destroy": (None, [P]),
         "ocn_model_halo": (I, [P, C.POINTER(C.c_int32 * 3)]),

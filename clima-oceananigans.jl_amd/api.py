@@ -245,6 +245,43 @@ class AdvectiveForcing:
         raise NotImplementedError("AdvectiveForcing is outside the path (an advection operator with its own velocities)")
 
 
+class BackgroundField:
+    """``BackgroundField(func; parameters)`` (Fields/background_fields.jl:63-67): ``func(x, y, z, t)`` or
+    ``func(x, y, z, t, parameters)``, evaluated at the nodes of the field it is the background of, halo nodes included (at the
+    extended node coordinates: never wrapped, never filled).  Field form (one parent-layout array, evaluated once, must not depend
+    on time) unless ``uniform_in_xy=True`` declares that it depends on ``(z, t)`` only: then it is column form, one table over
+    the parent levels, evaluated for every stage."""
+
+    def __init__(self, func, parameters=None, uniform_in_xy=False):
+        if not callable(func):
+            raise TypeError("BackgroundField: func must be a function of (x, y, z, t[, parameters])")
+        self.func, self.parameters, self.uniform_in_xy = func, parameters, bool(uniform_in_xy)
+
+    @property
+    def column(self):
+        return self.uniform_in_xy
+
+    def values(self, X, Y, Z, t, shape):
+        if self.parameters is None:
+            return _eval_nodes(self.func, shape, X, Y, Z, float(t))
+        return _eval_nodes(self.func, shape, X, Y, Z, float(t), self.parameters)
+
+
+class BackgroundFields:
+    """``model.background_fields``: ``velocities`` (u, v, w) and ``tracers`` (the model's), ``None`` for absent members (the
+    reference's ``ZeroField``)."""
+
+    def __init__(self, velocities, tracers):
+        self.velocities, self.tracers = velocities, tracers
+
+    def members(self):
+        """{name: member} of the members that are present"""
+        return {n: m for d in (self.velocities, self.tracers) for n, m in d.items() if m is not None}
+
+    def __bool__(self):
+        return bool(self.members())
+
+
 class BuoyancyTracer:
     tracers = ("b",)
 
@@ -482,7 +519,7 @@ class NonhydrostaticModel:
 
     def __init__(self, grid, advection=None, buoyancy=None, coriolis=None, closure=None,
                  boundary_conditions=None, tracers=(), timestepper="QuasiAdamsBashforth2", chi=0.1, stokes_drift=None,
-                 forcing=None):
+                 forcing=None, background_fields=None):
         self.grid, self.ctx, self.lib = grid, grid.ctx, grid.ctx.lib
         if stokes_drift is not None and not isinstance(stokes_drift, UniformStokesDrift):
             raise TypeError("stokes_drift must be a UniformStokesDrift or None")
@@ -580,7 +617,11 @@ class NonhydrostaticModel:
         self.forcing = self._regularize_forcing(forcing, names)
         self.forcing_uploads = 0           # column-table sets sent so far (one per stage slot whose contents changed)
         self._forcing_sent = [None] * 3    # what each stage slot holds
-        if self.forcing:
+        # background_fields: {name: function of (x, y, z, t) / BackgroundField / Field}, names among u, v, w and the tracers
+        self.background_fields = self._regularize_background(background_fields, names)
+        self.background_uploads = 0        # column-table sets sent so far (one per stage slot whose contents changed)
+        self._background_sent = [None] * 3
+        if self.forcing or self.background_fields:
             fd = L.ForcingDesc()
             for n, parts in self.forcing.items():
                 bit = 1 << names.index(n)
@@ -588,6 +629,12 @@ class NonhydrostaticModel:
                     fd.column_fields |= bit
                 if parts["fld_relax"] is not None or parts["fld_F"]:
                     fd.field_fields |= bit
+            bd = L.BackgroundDesc()
+            for n, mem in self.background_fields.members().items():
+                if isinstance(mem, BackgroundField) and mem.column:
+                    bd.column_members |= 1 << names.index(n)
+                else:
+                    bd.field_members |= 1 << names.index(n)
             sd = None
             if smag is not None:
                 sd = L.SmagorinskyLillyDesc()
@@ -596,9 +643,13 @@ class NonhydrostaticModel:
                     if isinstance(smag.Pr, dict) and n not in smag.Pr:
                         raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
                     sd.Pr[i] = smag.Pr_of(n)
-            check(self.lib.ocn_model_create_forced(grid.h, C.byref(d), C.byref(sd) if sd is not None else None,
-                                                   L.FEATURE_STOKES_DRIFT if stokes_drift is not None else 0, C.byref(fd),
-                                                   C.byref(self.h)), self.ctx.h)
+            features = L.FEATURE_STOKES_DRIFT if stokes_drift is not None else 0
+            if self.background_fields:
+                check(self.lib.ocn_model_create_background(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
+                                                           C.byref(fd), C.byref(bd), C.byref(self.h)), self.ctx.h)
+            else:
+                check(self.lib.ocn_model_create_forced(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
+                                                       C.byref(fd), C.byref(self.h)), self.ctx.h)
         elif smag is None and stokes_drift is None:
             check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
         elif smag is None:
@@ -634,6 +685,8 @@ class NonhydrostaticModel:
         self.Gm = {n: FieldView(self, L.F_GM + i, n) for i, n in enumerate(names)}
         if self.forcing:
             self._forcing_check_and_upload_fields()
+        if self.background_fields:
+            self._background_check_and_upload_fields()
 
     def __del__(self):
         try:
@@ -791,11 +844,127 @@ class NonhydrostaticModel:
             t, _, stage = self.clock
             self._forcing_set(stage - 1, t)
 
+    # ---- background fields: host evaluation of the members into the library's column tables and parent-layout arrays -------------
+    @staticmethod
+    def _regularize_background(background_fields, names):
+        if background_fields is None:
+            background_fields = {}
+        if not hasattr(background_fields, "items"):
+            raise TypeError("background_fields must be a mapping {name: function of (x, y, z, t), BackgroundField or Field}")
+        found = {}
+        for name, mem in background_fields.items():
+            if name not in names:
+                raise ValueError(f"background field {name} is neither a velocity (u, v, w) nor one of the model's tracers {names[3:]}")
+            if isinstance(mem, Field):
+                loc = {"u": (Face, Center, Center), "v": (Center, Face, Center), "w": (Center, Center, Face)}.get(name, (Center,) * 3)
+                if tuple(mem.loc) != loc:
+                    raise ValueError(f"Cannot use field at {mem.loc} as a background field at {loc}")
+            elif callable(mem) and not isinstance(mem, BackgroundField):
+                mem = BackgroundField(mem)                               # a bare function, as the reference wraps it
+            elif not isinstance(mem, BackgroundField):
+                raise TypeError(f"background field {name}: {mem!r} is neither a function of (x, y, z, t), a BackgroundField nor a Field")
+            found[name] = mem
+        return BackgroundFields({n: found.get(n) for n in names[:3]}, {n: found.get(n) for n in names[3:]})
+
+    def _axis_parent_nodes(self, a, face):
+        """coordinates of every parent node along axis ``a``, halo nodes at the extended coordinates (Grids/grid_generation.jl:28-107)"""
+        g, d = self.grid, self.grid.desc
+        N, H = g.N[a], self.halo[a]
+        if g.topo[a] == Flat:
+            return np.ones(1)
+        bounded = g.topo[a] == Bounded
+        TF, TC = N + 2 * H + (1 if bounded else 0), N + 2 * H
+        if a == 2 and g._zfaces is not None:
+            Fi = np.asarray(g._zfaces, dtype=np.float64)
+            if bounded:
+                dm, dp = np.full(H, Fi[1] - Fi[0]), np.full(H, Fi[-1] - Fi[-2])
+            else:
+                dm = np.array([Fi[N - H + i] - Fi[N - H + i - 1] for i in range(1, H + 1)])
+                dp = np.array([Fi[i] - Fi[i - 1] for i in range(1, H + 1)])
+            dp = dp[::-1]
+            Fm = np.array([Fi[0] - np.sum(dm[i:H]) for i in range(H)])
+            Fp = np.array([Fi[N] + np.sum(dp[i:H]) for i in range(H)])[::-1]
+            F = np.concatenate([Fm, Fi, Fp])
+            return F[:TF].copy() if face else np.array([(F[i + 1] + F[i]) / 2 for i in range(TC)])
+        dx = d.L[a] / N
+        return d.x0[a] + dx * (np.arange(TF) - H) if face else d.x0[a] + dx * (np.arange(TC) - H + 0.5)
+
+    def parent_nodes(self, name):
+        """node coordinates of every entry of the parent array of a prognostic field, halo entries included"""
+        X = self._axis_parent_nodes(0, name == "u").reshape(-1, 1, 1)
+        Y = self._axis_parent_nodes(1, name == "v").reshape(1, -1, 1)
+        Z = self._axis_parent_nodes(2, name == "w").reshape(1, 1, -1)
+        return X, Y, Z
+
+    def _background_column_table(self, name, t):
+        mem = self.background_fields.members()[name]
+        X, Y, Z = self.parent_nodes(name)
+        H = self.halo
+        x0, y0 = X[H[0]:H[0] + 1], Y[:, H[1]:H[1] + 1]
+        return mem.values(x0, y0, Z, t, (1, 1, Z.size)).ravel()
+
+    def _background_check_and_upload_fields(self):
+        g, t = self.grid, self.time
+        t2 = t + 0.7384                                                  # the probe of time independence
+        for name, mem in self.background_fields.members().items():
+            X, Y, Z = self.parent_nodes(name)
+            if isinstance(mem, Field):
+                self.set_background_field(name, mem.parent())
+                continue
+            if mem.column:                                               # uniform_in_xy is a declaration: look at a second (x, y)
+                H = self.halo
+                x0, y0 = X[H[0]:H[0] + 1], Y[:, H[1]:H[1] + 1]
+                shape1 = (1, 1, Z.size)
+                if not np.array_equal(mem.values(x0, y0, Z, t, shape1), mem.values(x0 + 0.377 * g.Lx, y0 + 0.291 * g.Ly, Z, t, shape1)):
+                    raise ValueError(f"background field {name}: declared uniform_in_xy=True but its values differ between two (x, y)")
+                continue
+            shape = (X.size, Y.size, Z.size)
+            v = mem.values(X, Y, Z, t, shape)
+            if not np.array_equal(v, mem.values(X, Y, Z, t2, shape)):
+                raise NotImplementedError(f"background field {name}: a background that depends on x or y and on time is outside the path "
+                                          "(a parent-array upload per stage); declare uniform_in_xy=True if it depends on (z, t) only")
+            self.set_background_field(name, v)
+
+    def set_background_field(self, name, array):
+        """replace the field-form array of member ``name``: the parent array of the field it belongs to, halo entries included.
+        Synchronises the model's stream."""
+        names = ("u", "v", "w") + self.tracer_names
+        total = (getattr(self, name) if name in "uvw" else self.tracers[name]).total
+        a = np.asarray(array, dtype=np.float64)
+        if a.shape != total:
+            raise ValueError(f"background field {name}: an array of shape {a.shape} for a parent array of shape {total} "
+                             "(a Field must live on a grid with the model's halo)")
+        a = np.asfortranarray(a)
+        check(self.lib.ocn_model_set_background_field(self.h, names.index(name), a.ctypes.data_as(C.POINTER(C.c_double)), *total), self.ctx.h)
+
+    def _background_set(self, slot, t):
+        names = ("u", "v", "w") + self.tracer_names
+        cols = [n for n, mem in self.background_fields.members().items() if isinstance(mem, BackgroundField) and mem.column]
+        if not cols:
+            return
+        tabs = {n: np.ascontiguousarray(self._background_column_table(n, t)) for n in cols}
+        sent = self._background_sent[slot]
+        changed = [n for n in cols if sent is None or not np.array_equal(tabs[n], sent[n])]
+        if not changed:
+            return
+        for n in changed:
+            check(self.lib.ocn_model_set_background_column(self.h, names.index(n), slot, tabs[n].ctypes.data_as(C.POINTER(C.c_double)),
+                                                           tabs[n].size), self.ctx.h)
+        self._background_sent[slot] = tabs
+        self.background_uploads += 1
+
+    def refresh_background(self):
+        """for the kernel-by-kernel verbs (``ocn_compute_tendencies`` ...): evaluate the column-form members at ``model.time`` into
+        the slot of the current stage.  ``time_step`` does this by itself for every stage of the step."""
+        if self.background_fields:
+            t, _, stage = self.clock
+            self._background_set(stage - 1, t)
+
     @property
     def kernel_path(self):
         """which kernels serve this model and, when it is not the fastest set, why"""
-        buf = C.create_string_buffer(512)
-        check(self.lib.ocn_model_path(self.h, buf, 512), self.ctx.h)
+        buf = C.create_string_buffer(768)
+        check(self.lib.ocn_model_path(self.h, buf, 768), self.ctx.h)
         return buf.value.decode()
 
     @property
@@ -874,6 +1043,9 @@ def time_step(model, dt, euler=False):
     if getattr(model, "forcing", None):
         for slot, t in enumerate(model.stage_times(dt)):
             model._forcing_set(slot, t)
+    if getattr(model, "background_fields", None):
+        for slot, t in enumerate(model.stage_times(dt)):
+            model._background_set(slot, t)
     check(model.lib.ocn_time_step(model.h, float(dt), int(bool(euler))), model.ctx.h)
 
 

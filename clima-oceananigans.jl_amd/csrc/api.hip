@@ -879,10 +879,25 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with and ocn_model_create_forced share this body
+// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with, ocn_model_create_forced and
+// ocn_model_create_background share this body
 static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes,
-                        const ocn_forcing_desc* forcing, ocn_model** out) {
+                        const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
   ocn_ctx* ctx = g->ctx;
+  const uint32_t bcol = background ? background->column_members : 0u, bfld = background ? background->field_members : 0u;
+  if ((bcol | bfld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((bcol | bfld) >> (3 + desc->n_tracers)) != 0)) {
+    ocn_set_error(ctx, "ocn_model_create_background: member masks 0x%x / 0x%x name members beyond u, v, w and the model's %d tracers", bcol, bfld,
+                  desc->n_tracers);
+    return OCN_EINVAL;
+  }
+  if (bcol & bfld) {
+    ocn_set_error(ctx, "ocn_model_create_background: members 0x%x are declared in both forms (a member has one)", bcol & bfld);
+    return OCN_EINVAL;
+  }
+  if ((bcol | bfld) && (g->dist || g->dist_y || ctx->nranks > 1)) {
+    ocn_set_error(ctx, "background fields on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) are not supported");
+    return OCN_EUNSUPPORTED;
+  }
   const uint32_t fcol = forcing ? forcing->column_fields : 0u, ffld = forcing ? forcing->field_fields : 0u;
   if ((fcol | ffld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((fcol | ffld) >> (3 + desc->n_tracers)) != 0)) {
     ocn_set_error(ctx, "ocn_model_create_forced: forcing masks 0x%x / 0x%x name fields beyond u, v, w and the model's %d tracers", fcol, ffld,
@@ -1065,6 +1080,30 @@ static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smago
       }
     }
   }
+  for (int f = 0; f < OCN_NF; ++f) m->bg_ci[f] = -1;
+  if (bcol | bfld) {
+    m->bg_col = bcol;
+    m->bg_fld = bfld;
+    m->bg_len = m->w.T[2] > m->u.T[2] ? m->w.T[2] : m->u.T[2];   // every parent level of the tallest field (w with a Bounded z)
+    for (int f = 0; f < 3 + m->nt; ++f)
+      if (bcol >> f & 1u) m->bg_ci[f] = m->bg_ncol++;
+    if (m->bg_ncol) {
+      const size_t nb = (size_t)3 * m->bg_ncol * m->bg_len * sizeof(double);
+      m->bg_stage = (double*)calloc(1, nb);
+      if (!m->bg_stage || hipMalloc((void**)&m->bg_dev, nb) != hipSuccess || hipMemset(m->bg_dev, 0, nb) != hipSuccess) {
+        ocn_model_destroy(m);
+        return OCN_ENOMEM;
+      }
+    }
+    for (int f = 0; f < 3 + m->nt; ++f) {   // field form: allocated here, zero until set, so the addresses in a step graph hold
+      if (!(bfld >> f & 1u)) continue;
+      const size_t nb = bg_field_of(m, f).n * sizeof(double);
+      if (hipMalloc((void**)&m->bg_arr[f], nb) != hipSuccess || hipMemset(m->bg_arr[f], 0, nb) != hipSuccess) {
+        ocn_model_destroy(m);
+        return OCN_ENOMEM;
+      }
+    }
+  }
   fused_read_knobs(m);
   m->fast_path = fused_available(m) ? 1 : 0;
   m->bz_fast = (!m->fast_path && fused_bz_available(m)) ? 1 : 0;
@@ -1103,7 +1142,7 @@ extern "C" {
 int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
   if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-  return model_create(g, desc, nullptr, false, nullptr, out);
+  return model_create(g, desc, nullptr, false, nullptr, nullptr, out);
 }
 
 int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
@@ -1116,8 +1155,14 @@ int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_sma
 
 int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
                             const ocn_forcing_desc* forcing, ocn_model** out) {
+  return ocn_model_create_background(g, desc, smag, features, forcing, nullptr, out);
+}
+
+int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                                const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
   if (forcing && !(forcing->column_fields | forcing->field_fields)) forcing = nullptr;
+  if (background && !(background->column_members | background->field_members)) background = nullptr;
   if (features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
     ocn_set_error(g->ctx, "ocn_model_create_with: unknown feature bits 0x%x", features);
     return OCN_EINVAL;
@@ -1125,7 +1170,7 @@ int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_s
   const bool stokes = (features & OCN_FEATURE_STOKES_DRIFT) != 0;
   if (!smag) {
     if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-    return model_create(g, desc, nullptr, stokes, forcing, out);
+    return model_create(g, desc, nullptr, stokes, forcing, background, out);
   }
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
@@ -1158,7 +1203,7 @@ int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_s
     ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
     return OCN_EINVAL;
   }
-  return model_create(g, desc, smag, stokes, forcing, out);
+  return model_create(g, desc, smag, stokes, forcing, background, out);
 }
 
 int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,
@@ -1273,6 +1318,65 @@ int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, co
   return api_ret(m->ctx, OCN_OK);
 }
 
+static int background_member_index(ocn_model* m, const char* who, int member) {
+  if (member < 0 || member >= 3 + m->nt) {
+    ocn_set_error(m->ctx, "%s: member %d is outside 0..%d (u, v, w, then the model's tracers)", who, member, 2 + m->nt);
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+
+int ocn_model_set_background_column(ocn_model* m, int member, int stage, const double* table, int n) {
+  if (!m) return OCN_EINVAL;
+  if (int rc = background_member_index(m, "ocn_model_set_background_column", member)) return rc;
+  if (!(m->bg_col >> member & 1u)) {
+    ocn_set_error(m->ctx, "ocn_model_set_background_column: member %d was not declared in ocn_background_desc.column_members at creation", member);
+    return OCN_ESTATE;
+  }
+  if (stage < 0 || stage > 2) {
+    ocn_set_error(m->ctx, "ocn_model_set_background_column: stage %d is outside 0..2", stage);
+    return OCN_EINVAL;
+  }
+  const int Tz = bg_field_of(m, member).T[2];
+  if (n != Tz || !table) {
+    ocn_set_error(m->ctx, "ocn_model_set_background_column: a table of %d entries for a field of %d parent levels (Nz + 2 Hz, + 1 for w with a Bounded z)",
+                  table ? n : 0, Tz);
+    return OCN_EINVAL;
+  }
+  // library-owned staging, as ocn_model_set_stokes_drift: wait for this (slot, member)'s previous copy alone, never for the stream
+  const size_t at = ((size_t)stage * m->bg_ncol + m->bg_ci[member]) * m->bg_len;
+  double* st = m->bg_stage + at;
+  hipEvent_t& ev = m->bg_ev[stage][member];
+  if (ev) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(ev));
+  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&ev));
+  memcpy(st, table, (size_t)Tz * sizeof(double));
+  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->bg_dev + at, st, (size_t)Tz * sizeof(double), hipMemcpyHostToDevice, m->ctx->stream));
+  OCN_HIP_CHECK(m->ctx, hipEventRecord(ev, m->ctx->stream));
+  return api_ret(m->ctx, OCN_OK);
+}
+
+int ocn_model_set_background_field(ocn_model* m, int member, const double* array, int tx, int ty, int tz) {
+  if (!m) return OCN_EINVAL;
+  if (int rc = background_member_index(m, "ocn_model_set_background_field", member)) return rc;
+  if (!(m->bg_fld >> member & 1u)) {
+    ocn_set_error(m->ctx, "ocn_model_set_background_field: member %d was not declared in ocn_background_desc.field_members at creation", member);
+    return OCN_ESTATE;
+  }
+  const Field& f = bg_field_of(m, member);   // the layout the kernels' strides address
+  if (!array || tx != f.T[0] || ty != f.T[1] || tz != f.T[2]) {
+    ocn_set_error(m->ctx, "ocn_model_set_background_field: an array of (%d, %d, %d) for a parent array of (%d, %d, %d)", array ? tx : 0, array ? ty : 0,
+                  array ? tz : 0, f.T[0], f.T[1], f.T[2]);
+    return OCN_EINVAL;
+  }
+  if (halo_settle(m)) return OCN_EHIP;
+  OCN_HIP_CHECK(m->ctx, hipStreamSynchronize(m->ctx->stream));   // no launch in flight reads the array being replaced
+  std::vector<double> phys(f.n, 0.0);
+  const int lo[3] = {0, 0, 0};
+  host_scatter(f, array, lo, f.T, phys);
+  OCN_HIP_CHECK(m->ctx, hipMemcpy(m->bg_arr[member], phys.data(), f.n * sizeof(double), hipMemcpyHostToDevice));
+  return api_ret(m->ctx, OCN_OK);
+}
+
 int ocn_model_stage_times(const ocn_model* m, double dt, double times[3], int32_t* nstages) {
   if (!m || !times || !nstages) return OCN_EINVAL;
   times[0] = times[1] = times[2] = m->time;
@@ -1332,6 +1436,13 @@ void ocn_model_destroy(ocn_model* m) {
       if (m->force_ev[s][f]) hipEventDestroy(m->force_ev[s][f]);
       hipFree(m->force_arr[f][s]);
     }
+  }
+  hipFree(m->bg_dev);
+  free(m->bg_stage);
+  for (int f = 0; f < OCN_NF; ++f) {
+    for (int s = 0; s < 3; ++s)
+      if (m->bg_ev[s][f]) hipEventDestroy(m->bg_ev[s][f]);
+    hipFree(m->bg_arr[f]);
   }
   hipFree(m->ypack_s);
   hipFree(m->ypack_r);

@@ -1108,6 +1108,7 @@ static bool fused_available_but_for_stokes(const ocn_model* m) {
 bool fused_available(const ocn_model* m) {
   if (m->stokes) return false;   // UniformStokesDrift: its terms live in k_rest4 / k_tend_uvw, like Coriolis
   if (model_forced(m)) return false;   // forcing: its terms live in k_rest4 / k_tracer_step3<REST> / k_tend_uvw / k_tend_c
+  if (model_background(m)) return false;   // background fields: their terms join G^n in launches of their own (background.hip)
   return fused_available_but_for_stokes(m);
 }
 
@@ -1145,6 +1146,16 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
     snprintf(buf + l, n - l, "; %sforcing terms are served by %s%s%s", !m->stokes && fused_available_but_for_stokes(m) ? "not the all-in-one periodic path: " : "",
              !mom ? "" : rest4_ok(m) ? "k_rest4" : "the general kernel (k_tend_uvw)", mom && trc ? " and " : "",
              !trc ? "" : tr3 ? "k_tracer_step3 (REST)" : "the general kernel (k_tend_c)");
+  }
+  if (model_background(m)) {   // what adds the two background advection terms, in which forms, and whether they alone keep the model off the all-in-one path
+    const size_t l = strlen(buf);
+    const uint32_t all = m->bg_col | m->bg_fld;
+    const bool mom = (all & 7u) != 0, trc = m->nt > 0 && all != 0;
+    const char* form = !m->bg_fld ? "column form" : !m->bg_col ? "field form" : "column and field form";
+    snprintf(buf + l, n - l, "; %sbackground-field terms are served by %s%s%s (%s)%s",
+             !m->stokes && !model_forced(m) && fused_available_but_for_stokes(m) ? "not the all-in-one periodic path: " : "",
+             mom ? "k_bg_uvw" : "", mom && trc ? " and " : "", trc ? "k_bg_c" : "", form,
+             m->d.advection == ADV_NONE ? ", which launch nothing without an advection scheme" : "");
   }
   if (m->d.closure == OCN_CLOSURE_SMAG) {
     const size_t l = strlen(buf);
@@ -1514,7 +1525,8 @@ int fused_exchange_phi(ocn_model* m, const double* phi) {
 
 // G^n of a tracer arrives holding only boundary fluxes when the tiled kernel carries advection and closure; without walls in
 // x / y those live in the first and last level, so only these two planes are cleared and read (kernels.hip launch_tendencies)
-bool tracer_rest_shell(const ocn_model* m) { return !m->gd.xb && !m->gd.yb; }
+// With background fields every level of G^n carries a term before the tiled tracer kernel reads it: the full-array form.
+bool tracer_rest_shell(const ocn_model* m) { return !m->gd.xb && !m->gd.yb && !model_background(m); }
 
 bool fused_tracer3_ok(const ocn_model* m) {
   return m->gd.Nx <= 256 && !m->gd.xb && !m->knob_no_tracer3;

@@ -175,6 +175,18 @@ struct ocn_model {
   double* force_stage = nullptr;    // host staging of the same shape
   hipEvent_t force_ev[3][OCN_NF] = {};   // recorded behind each (slot, field) upload
   double* force_arr[OCN_NF][3] = {};     // field form: sigma, tau, F
+  // BackgroundFields (ocn_model_create_background): G_phi -= div(adv, (U, V, W), phi) + div(adv, (u, v, w), Phi) with background
+  // velocities U, V, W (members 0, 1, 2) and background tracers (member 3 + t).  A member has one form.  Column form: bg_dev holds,
+  // per stage slot and declared member (bg_ci[f]: its rank among them), one table of bg_len doubles of which the first T[2] of
+  // the member's field are used -- every parent level, halo levels included; the device addresses never change, so a captured
+  // step graph reads the current contents.  Field form: one array in the layout of the parent array of the field it belongs to,
+  // allocated at creation (zero until set), so its address never changes either.
+  uint32_t bg_col = 0, bg_fld = 0;
+  int bg_ncol = 0, bg_ci[OCN_NF], bg_len = 0;
+  double* bg_dev = nullptr;        // [3][bg_ncol][bg_len]
+  double* bg_stage = nullptr;      // host staging of the same shape
+  hipEvent_t bg_ev[3][OCN_NF] = {};   // recorded behind each (slot, member) upload
+  double* bg_arr[OCN_NF] = {};     // field form
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
 };
@@ -212,7 +224,14 @@ inline ForceDev force_of(const ocn_model* m, int f, bool interior) {
   return fo;
 }
 
+inline bool model_background(const ocn_model* m) { return (m->bg_col | m->bg_fld) != 0; }
+// the field whose nodes and parent layout background member f has (0, 1, 2: u, v, w; 3 + t: tracer t)
+inline const Field& bg_field_of(const ocn_model* m, int f) { return f == 0 ? m->u : f == 1 ? m->v : f == 2 ? m->w : m->tr[f - 3]; }
+
 Field* model_field(ocn_model* m, int id);
+
+// ---- background.hip ---------------------------------------------------------------------------------
+void launch_background(ocn_model* m);   // adds the background-field advection terms to G^n of u, v, w and the tracers
 
 // ---- kernels.hip ------------------------------------------------------------------------------------
 struct FieldPtrs {   // up to velocities + both pressures + all tracers in one call (ocn_fill_halos)

@@ -329,6 +329,9 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
       ocn_launch(k_apply_flux, g2, b2, s, g, m->Gn[f].interior(), dim, fld->loc[2], l_, h_);
     }
   }
+  // BackgroundFields: both advection terms join G^n in launches of their own (background.hip), after the kernels above (or
+  // k_rest4) wrote it and before k_step / k_tend4 / k_tracer_step3<REST> consume it
+  launch_background(m);
 }
 
 // ---- time stepping (ab2_step_field!, rk3_substep_field!, store_field_tendencies!) ------------------

@@ -128,9 +128,10 @@ typedef struct ocn_bc {
 /* NonhydrostaticModel(; grid, advection, buoyancy, coriolis, closure, boundary_conditions, tracers,
  * timestepper) -- Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203.  A UniformStokesDrift and forcings without field
  * dependencies (Relaxation, ContinuousForcing) are user functions that the caller evaluates into tables and arrays
- * (ocn_model_create_with, ocn_model_create_forced).  Forcings with field dependencies, discrete-form and advective forcings,
- * background fields, immersed boundaries and particles are user Julia closures / out of scope: not representable across a C
- * ABI, the shim rejects them. */
+ * (ocn_model_create_with, ocn_model_create_forced).  Background fields are user functions too: the caller evaluates them into
+ * column tables and parent-layout arrays (ocn_model_create_background).  Forcings with field dependencies, discrete-form and
+ * advective forcings, background fields that vary in x or y and in time, immersed boundaries and particles are user Julia
+ * closures / out of scope: not representable across a C ABI, the shim rejects them. */
 typedef struct ocn_model_desc {
   int32_t advection;   /* OCN_ADV_*                                   */
   int32_t stepper;     /* OCN_STEPPER_*                               */
@@ -240,6 +241,44 @@ int ocn_model_set_forcing_column(ocn_model* m, int field, int stage, const doubl
  * then replaces the arrays; callable between steps.  OCN_ESTATE: the field was not declared in field_fields; OCN_EINVAL: field
  * out of range, (nx, ny, nz) != (Nx, Ny, Nz). */
 int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, const double* tau, const double* F, int nx, int ny, int nz);
+/* NonhydrostaticModel(; background_fields = (u = U, b = B, ...)) -- Fields/background_fields.jl:5-75,
+ * nonhydrostatic_tendency_kernel_functions.jl:61-63,118-120,172-174,226-228, momentum_advection_operators.jl:20-86,
+ * tracer_advection_operators.jl:8-35.  With (U, V, W) the background velocities and Phi the background of phi, for u, v, w and
+ * every tracer phi, with the model's own advection scheme and boundary buffers and t = clock.time of the stage:
+ *     G_phi += - div(adv, (U, V, W), phi) - div(adv, (u, v, w), Phi)
+ * The upwind bias follows the advecting velocity: the interpolated background velocity in the first term, the interpolated model
+ * velocity in the second.  An absent member is the reference's ZeroField: no background velocity at all -> no first term; no
+ * background of phi -> no second term of phi; advection = nothing -> neither.  Nothing else sees the background (closure, buoyancy,
+ * Coriolis, pressure, halo fills).  A member is a function evaluated at the nodes of the field it belongs to -- U at (Face, Center,
+ * Center), V at (Center, Face, Center), W at (Center, Center, Face), tracers at centres -- INCLUDING the halo nodes, at the
+ * extended node coordinates: never wrapped periodically, never filled by boundary conditions.  The functions cannot cross this
+ * boundary; the caller evaluates each member in one of two forms:
+ *   column form -- the member depends on (z, t): one table per stage slot over the parent levels of its field, Nz + 2 Hz entries
+ *     (+ 1 for w with a Bounded z; Hz of ocn_model_halo), read as wave-uniform scalars; it may change every stage
+ *     (ocn_model_set_background_column);
+ *   field form  -- one array in the layout of the logical parent array of its field (ocn_field_shape's totals), constant in time
+ *     (ocn_model_set_background_field).
+ * Bit f of either mask stands for member f: 0, 1, 2 are U, V, W and 3 + t is the background of tracer t.  Background fields are
+ * a creation-time property: they decide the kernels (never the all-in-one periodic path; ocn_model_path says so) and allocate the
+ * storage whose device addresses never change.  Everything is zero until set.  background == NULL or both masks zero: exactly
+ * ocn_model_create_forced.  OCN_EINVAL: a bit beyond the model's fields, a member in both masks; OCN_EUNSUPPORTED: a distributed
+ * grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST).  Flat directions are allowed. */
+typedef struct ocn_background_desc {
+  uint32_t column_members, field_members;
+} ocn_background_desc;
+int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                                const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out);
+/* Column-form table of `member` for the tendency evaluation of stage `stage` (0..2; QuasiAdamsBashforth2 uses 0; the
+ * kernel-by-kernel verbs read slot `stage of ocn_clock` - 1): the member at the z nodes of every parent level of its field,
+ * bottom halo first, n entries.  The values are copied before the call returns and uploaded on the model's stream; the device
+ * address of a slot never changes, so a replayed step graph reads whatever was set last.  OCN_ESTATE: the member was not declared
+ * in column_members; OCN_EINVAL: member or stage out of range, table NULL, n != the field's parent levels. */
+int ocn_model_set_background_column(ocn_model* m, int member, int stage, const double* table, int n);
+/* Field-form array of `member`: the member at every node of the logical parent array of its field, column-major (tx, ty, tz) as
+ * ocn_field_shape reports the totals; a Flat x / y direction has one entry.  Synchronises the model's stream, then replaces the
+ * contents (the device address stays); callable between steps.  OCN_ESTATE: the member was not declared in field_members;
+ * OCN_EINVAL: member out of range, array NULL, (tx, ty, tz) != the parent's totals. */
+int ocn_model_set_background_field(ocn_model* m, int member, const double* array, int tx, int ty, int tz);
 void ocn_model_destroy(ocn_model* m);
 /* which kernels serve this model, and if not the fastest ones, why (e.g. "general kernels: parent arrays of 2 GiB or
  * more exceed the tiled kernels' 32-bit byte offsets").  Writes at most n bytes incl. the terminating 0. */

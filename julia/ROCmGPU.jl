@@ -92,7 +92,7 @@ function bc_of(bc, keep)
 end
 
 function ocn_model(arch::ROCmGPU, gridh, m)                                             # m: the fields NonhydrostaticModel(...) assembled
-    isempty(m.background_fields) || error("background fields are Julia closures: outside the C ABI")
+    bplan = background_plan(m)                                                          # which members exist and in which form
     fplan = forcing_plan(m)                                                             # refuses what cannot be tabulated, by name
     m.stokes_drift === nothing || m.stokes_drift isa UniformStokesDrift || error("stokes_drift: only UniformStokesDrift is on the path")
     names = keys(m.tracers); nt = length(names)
@@ -123,7 +123,12 @@ function ocn_model(arch::ROCmGPU, gridh, m)                                     
                      closure == 2 ? sides(m.diffusivity_fields.νₑ) : none,
                      ntuple(i -> (closure == 2 && i <= nt) ? sides(m.diffusivity_fields.κₑ[i]) : none, MAXTR))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if fplan.column_fields | fplan.field_fields != 0   # forcing is a creation-time property too: ocn_forcing_desc { column_fields, field_fields }
+    if bplan.column_members | bplan.field_members != 0   # background fields: ocn_background_desc { column_members, field_members }; forcing rides along
+        fd = UInt32[fplan.column_fields, fplan.field_fields]; bd = UInt32[bplan.column_members, bplan.field_members]
+        GC.@preserve keep fd bd check(ccall((:ocn_model_create_background, libocnhip), Cint,
+                                            (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ptr{UInt32}, Ptr{UInt32}, Ref{Ptr{Cvoid}}),
+                                            gridh, desc, C_NULL, UInt32(m.stokes_drift === nothing ? 0 : 1), fd, bd, h), arch.ctx)
+    elseif fplan.column_fields | fplan.field_fields != 0   # forcing is a creation-time property too: ocn_forcing_desc { column_fields, field_fields }
         fd = UInt32[fplan.column_fields, fplan.field_fields]
         GC.@preserve keep fd check(ccall((:ocn_model_create_forced, libocnhip), Cint,
                                          (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ptr{UInt32}, Ref{Ptr{Cvoid}}),
@@ -276,10 +281,69 @@ function refresh_forcing!(model::RM, Δt)            # before ocn_time_step, lik
     end
 end
 
+# background_fields = (u = U, b = BackgroundField(B, parameters = p), ...) (Fields/background_fields.jl:5-75,
+# nonhydrostatic_tendency_kernel_functions.jl:61-63,118-120,172-174,226-228): G_phi += -div(adv, (U, V, W), phi) - div(adv, (u, v, w), Phi).
+# model.background_fields holds a FunctionField (or a user's Field, or a ZeroField) per member at the member's location; the kernels read
+# it over the PARENT index range -- halo nodes at their extended coordinates -- so that is what is evaluated here.  Member f: 0, 1, 2 are
+# U, V, W, 3 + t is the background of tracer t.  A FunctionField that gives the same column at two (x, y) is sent in the column form (one
+# table over the parent levels per stage, may vary in time); everything else in the field form (the whole parent array, once; a probe at a
+# second time must agree; a Field's parent array as it stands).  Not run: no Julia toolchain exists where this was written.
+using Oceananigans.Fields: ZeroField, FunctionField
+background_members(m) = ((:u, m.background_fields.velocities.u), (:v, m.background_fields.velocities.v), (:w, m.background_fields.velocities.w),
+                         ((n, m.background_fields.tracers[n]) for n in keys(m.tracers))...)
+parent_range(f, d) = (g = f.grid; N = size(g)[d]; H = halo_size(g)[d]; topology(g, d) === Flat ? (1:1) :
+                      (1 - H):(N + H + (location(f)[d] === Face && topology(g, d) === Bounded ? 1 : 0)))
+at_time(f::FunctionField, t) = FunctionField{location(f)...}(f.func, f.grid; clock = (time = t,), parameters = f.parameters)
+column_of(f, i, j) = Float64[f[i, j, k] for k in parent_range(f, 3)]
+is_column(f) = f isa FunctionField && column_of(f, 1, 1) == column_of(f, 1 + size(f.grid)[1] ÷ 3, 1 + size(f.grid)[2] ÷ 3)
+function background_plan(m)
+    col, fld = UInt32(0), UInt32(0); members = Dict{Symbol, Any}()
+    for (i, (n, f)) in enumerate(background_members(m))
+        f isa ZeroField && continue
+        is_column(f) ? (col |= UInt32(1) << (i - 1)) : (fld |= UInt32(1) << (i - 1))
+        members[n] = (i - 1, f)
+    end
+    return (column_members = col, field_members = fld, members = members)
+end
+function set_background_columns!(model::RM, slot, t, sent)    # model.auxiliary_fields.background_plan / background_sent = Any[nothing, nothing, nothing]
+    plan = model.auxiliary_fields.background_plan; tabs = Dict{Symbol, Any}()
+    for (n, (f, mem)) in plan.members
+        (plan.column_members >> f) & 1 == 1 && (tabs[n] = column_of(at_time(mem, t), 1, 1))
+    end
+    for (n, tab) in tabs
+        sent[slot + 1] !== nothing && get(sent[slot + 1], n, nothing) == tab && continue
+        check(ccall((:ocn_model_set_background_column, libocnhip), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Cint),
+                    handle(model), plan.members[n][1], slot, tab, length(tab)), model.architecture.ctx)
+    end
+    sent[slot + 1] = tabs
+    return nothing
+end
+function set_background_fields!(model::RM)                    # once, after construction: the field form is constant in time
+    plan = model.auxiliary_fields.background_plan; t = model.clock.time
+    for (n, (f, mem)) in plan.members
+        (plan.field_members >> f) & 1 == 1 || continue
+        ev(fld) = Float64[fld[i, j, k] for i in parent_range(fld, 1), j in parent_range(fld, 2), k in parent_range(fld, 3)]
+        a = mem isa FunctionField ? ev(at_time(mem, t)) : Array{Float64}(parent(mem))
+        mem isa FunctionField && a != ev(at_time(mem, t + 0.7384)) &&
+            error("background field $n: a background that depends on x or y and on time is outside the path (a parent-array upload per stage)")
+        GC.@preserve a check(ccall((:ocn_model_set_background_field, libocnhip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cint, Cint),
+                                   handle(model), f, a, size(a)...), model.architecture.ctx)
+    end
+end
+function refresh_background!(model::RM, Δt)         # before ocn_time_step, like refresh_forcing!
+    isempty(model.auxiliary_fields.background_plan.members) && return nothing
+    times = zeros(3); n = Ref(Int32(0))
+    check(ccall((:ocn_model_stage_times, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Float64}, Ref{Int32}), handle(model), Δt, times, n))
+    for s in 1:n[]
+        set_background_columns!(model, s - 1, times[s], model.auxiliary_fields.background_sent)
+    end
+end
+
 # TimeSteppers/quasi_adams_bashforth_2.jl:70-104 and runge_kutta_3.jl:81-152 -- preferred, coarsest overload
 function time_step!(model::RM, Δt; euler=false)
     refresh_stokes_drift!(model, Δt)
     refresh_forcing!(model, Δt)
+    refresh_background!(model, Δt)
     check(ccall((:ocn_time_step, libocnhip), Cint, (Ptr{Cvoid}, Cdouble, Cint), handle(model), Δt, euler), model.architecture.ctx)
     # clock mirrors ocn_clock (TimeSteppers/clock.jl:48-60)
     t = Ref(0.0); it = Ref(Int64(0)); st = Ref(Int32(0))
