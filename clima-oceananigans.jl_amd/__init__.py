@@ -10,6 +10,7 @@ All numerical work happens in libocnhip.so (hand-written HIP for gfx950 + hipFFT
 from .api import (Context, RectilinearGrid, NonhydrostaticModel, Periodic, Bounded, Flat, Center, Face,  # noqa: F401
                   WENO5, NoAdvection, CenteredSecondOrder, CenteredFourthOrder, UpwindBiasedFifthOrder, UpwindBiasedFirstOrder, UpwindBiasedThirdOrder, ScalarDiffusivity,
                   AnisotropicMinimumDissipation, SmagorinskyLilly, UniformStokesDrift, Relaxation, GaussianMask, LinearTarget, Forcing, AdvectiveForcing, BackgroundField, FPlane, BuoyancyTracer, SeawaterBuoyancy,
+                  Buoyancy, ConstantCartesianCoriolis, QuadraticDragBC, ZDirection, validate_unit_vector,
                   FluxBC, ValueBC, GradientBC, Field, CenterField, time_step, set_model, update_state, OcnError)
 from . import _lib  # noqa: F401
 from . import hydrostatic  # noqa: F401   SplitExplicitFreeSurface, LatitudeLongitudeGrid (BASELINE config 5, first slice)

@@ -60,6 +60,16 @@ class BackgroundDesc(C.Structure):
     _fields_ = [("column_members", C.c_uint32), ("field_members", C.c_uint32)]
 
 
+class QuadraticDrag(C.Structure):
+    _fields_ = [("present", C.c_int32), ("cd", C.c_double), ("u_background", C.c_double), ("v_background", C.c_double)]
+
+
+class TiltedDesc(C.Structure):
+    _fields_ = [("has_gravity_vector", C.c_int32), ("gx", C.c_double), ("gy", C.c_double), ("gz", C.c_double),
+                ("coriolis_cartesian", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("fz", C.c_double),
+                ("drag", (QuadraticDrag * 2) * 2)]   # [u, v][bottom, top]
+
+
 class HydroDesc(C.Structure):
     _fields_ = [("free_surface", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("w", C.c_void_p), ("pHY", C.c_void_p),
                 ("ntracers", C.c_int32), ("tracers", C.POINTER(C.c_void_p)), ("Gn", C.POINTER(C.c_void_p)), ("Gm", C.POINTER(C.c_void_p)),
@@ -120,6 +130,8 @@ def load():
         "ocn_model_set_forcing_field": (I, [P, I, PD, PD, PD, I, I, I]),
         "ocn_model_create_background": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(ForcingDesc),
                                             C.POINTER(BackgroundDesc), C.POINTER(P)]),
+        "ocn_model_create_tilted": (I, [P, C.POINTER(ModelDesc), C.POINTER(SmagorinskyLillyDesc), C.c_uint32, C.POINTER(ForcingDesc),
+                                        C.POINTER(BackgroundDesc), C.POINTER(TiltedDesc), C.POINTER(P)]),
         "ocn_model_set_background_column": (I, [P, I, I, PD, I]),
         "ocn_model_set_background_field": (I, [P, I, PD, I, I, I]),
         "ocn_model_stage_times": (I, [P, D, C.POINTER(C.c_double * 3), C.POINTER(C.c_int32)]),

@@ -108,6 +108,57 @@ class FPlane:
         self.f = float(f)
 
 
+class _ZDirection:
+    """``ZDirection()`` (Grids/Grids.jl): the default rotation axis and gravity direction, a type of its own, not ``(0, 0, 1)``."""
+
+    def __repr__(self):
+        return "ZDirection"
+
+
+ZDirection = _ZDirection()
+OMEGA_EARTH = 7.292115e-5   # Coriolis/Coriolis.jl:13, the value the hydrostatic mirror uses
+
+
+def validate_unit_vector(e):
+    """``validate_unit_vector`` (Grids/input_validation.jl:176-187): ``ZDirection`` passes; anything else must have three entries
+    with ``ex^2 + ey^2 + ez^2`` ≈ 1 by Julia's ``isapprox`` default, ``|s - 1| <= sqrt(eps) * max(s, 1)``.  Returns a tuple."""
+    if e is ZDirection:
+        return e
+    try:
+        e = tuple(float(x) for x in e)
+    except TypeError:
+        raise ValueError("unit vector must have length 3") from None
+    if len(e) != 3:
+        raise ValueError("unit vector must have length 3")
+    s2 = e[0] ** 2 + e[1] ** 2 + e[2] ** 2
+    if not abs(s2 - 1.0) <= np.sqrt(np.finfo(np.float64).eps) * max(s2, 1.0):
+        raise ValueError("unit vector `e` must have e[1]^2 + e[2]^2 + e[3]^2 ≈ 1")
+    return e
+
+
+class ConstantCartesianCoriolis:
+    """``ConstantCartesianCoriolis(; fx, fy, fz, f, rotation_axis=ZDirection(), rotation_rate=Ω_Earth, latitude)``
+    (Coriolis/constant_cartesian_coriolis.jl:31-63): a constant rotation vector with all three components, given as the three
+    components, as ``f`` about a validated ``rotation_axis``, or as a ``latitude`` in degrees with a ``rotation_rate``."""
+
+    def __init__(self, fx=None, fy=None, fz=None, f=None, rotation_axis=ZDirection, rotation_rate=OMEGA_EARTH, latitude=None):
+        if latitude is not None:
+            if not all(x is None for x in (fx, fy, fz, f)):
+                raise ValueError("Only `rotation_rate` can be specified when using `latitude`.")
+            phi = np.deg2rad(float(latitude))
+            fx, fy, fz = 0.0, 2 * rotation_rate * np.cos(phi), 2 * rotation_rate * np.sin(phi)
+        elif f is not None:
+            if not all(x is None for x in (fx, fy, fz)):
+                raise ValueError("Only `rotation_axis` can be specified when using `f`.")
+            axis = validate_unit_vector(rotation_axis)
+            fx, fy, fz = (0.0, 0.0, f) if axis is ZDirection else (f * axis[0], f * axis[1], f * axis[2])
+        elif all(x is not None for x in (fx, fy, fz)):
+            pass
+        else:
+            raise ValueError("Either (i) `latitude`, or (ii) `f`, or (iii) `fx`, `fy` and `fz` must be specified.")
+        self.fx, self.fy, self.fz = float(fx), float(fy), float(fz)
+
+
 class UniformStokesDrift:
     """``UniformStokesDrift(; ∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ)`` (StokesDrift.jl:46-62): four functions ``f(z, t)``; ``None`` is the
     reference's ``addzero``.  The functions are evaluated on the host at the z nodes and at the clock time of each stage; the
@@ -294,9 +345,39 @@ class SeawaterBuoyancy:
         self.g, self.alpha, self.beta = gravitational_acceleration, thermal_expansion, haline_contraction
 
 
+class Buoyancy:
+    """``Buoyancy(; model, gravity_unit_vector=ZDirection())`` (BuoyancyModels/buoyancy.jl:30-33): ``model`` is a
+    ``BuoyancyTracer`` or a ``SeawaterBuoyancy``; the vector points opposite to gravity.  Three numbers take the tilted kernels,
+    ``(0, 0, 1)`` included; only ``ZDirection`` is the plain model."""
+
+    def __init__(self, model, gravity_unit_vector=ZDirection):
+        if not isinstance(model, (BuoyancyTracer, SeawaterBuoyancy)):
+            raise TypeError("Buoyancy: model must be a BuoyancyTracer or a SeawaterBuoyancy")
+        self.model, self.gravity_unit_vector = model, validate_unit_vector(gravity_unit_vector)
+
+    @property
+    def tracers(self):
+        return self.model.tracers
+
+
 class _BC:
     def __init__(self, kind, condition):
         self.kind, self.condition = kind, condition
+
+
+class QuadraticDragBC(_BC):
+    """The quadratic drag of ``examples/tilted_bottom_boundary_layer.jl`` as a built-in Flux condition (its
+    ``FluxBoundaryCondition(drag_u, field_dependencies = (:u, :v), parameters = (; cᴰ, V∞))`` is a user function, which cannot run
+    on the device).  On ``u``: ``((-cd) sqrt(U U + V V)) U``, on ``v``: ``... V``, with ``U = u + u_background``,
+    ``V = v + v_background`` at the location of the field that carries the condition and the boundary-adjacent level.  Accepted on
+    the ``bottom`` and ``top`` of ``u`` and ``v``."""
+
+    def __init__(self, cd, u_background=0.0, v_background=0.0):
+        for n, x in (("cd", cd), ("u_background", u_background), ("v_background", v_background)):
+            if not _is_number(x) or not np.isfinite(x):
+                raise ValueError(f"QuadraticDragBC: {n} must be a finite number")
+        super().__init__(L.BC_FLUX, None)
+        self.cd, self.u_background, self.v_background = float(cd), float(u_background), float(v_background)
 
 
 def FluxBC(v):
@@ -560,9 +641,19 @@ class NonhydrostaticModel:
                 d.amd_Ckappa[i] = float(closure.Ckappa[n] if isinstance(closure.Ckappa, dict) else closure.Ckappa)
         else:
             raise OcnError("OCN_EUNSUPPORTED: closure outside the path")
-        if coriolis is not None:
+        td = L.TiltedDesc()                # tilted gravity, Cartesian Coriolis, quadratic drag: ocn_model_create_tilted when any is set
+        if isinstance(coriolis, ConstantCartesianCoriolis):
+            td.coriolis_cartesian, td.fx, td.fy, td.fz = 1, coriolis.fx, coriolis.fy, coriolis.fz
+        elif coriolis is not None:
             d.coriolis_fplane, d.f = 1, float(coriolis.f)
+        self.coriolis = coriolis
         d.b_index = d.T_index = d.S_index = -1
+        self.buoyancy = buoyancy
+        if isinstance(buoyancy, Buoyancy):     # regularize_buoyancy: a bare model stays what it is
+            if buoyancy.gravity_unit_vector is not ZDirection:
+                td.has_gravity_vector = 1
+                td.gx, td.gy, td.gz = buoyancy.gravity_unit_vector
+            buoyancy = buoyancy.model
         if buoyancy is None:
             d.buoyancy = L.BUOYANCY_NONE
         else:
@@ -579,6 +670,8 @@ class NonhydrostaticModel:
         self._keep = []
         names = ("u", "v", "w") + self.tracer_names
         def fill(slot, side, bc):
+            if isinstance(bc, QuadraticDragBC):
+                raise ValueError(f"QuadraticDragBC on the {side} of a diffusivity field: it is offered on the bottom and top of u and v")
             b = slot[_SIDES[side]]
             b.kind = bc.kind
             if np.isscalar(bc.condition):
@@ -610,7 +703,15 @@ class NonhydrostaticModel:
             if fname not in names:
                 raise ValueError(f"boundary conditions for unknown field {fname}")
             for side, bc in sides.items():
-                fill(d.bcs[names.index(fname)], side, bc)
+                if isinstance(bc, QuadraticDragBC):
+                    if fname not in ("u", "v") or side not in ("bottom", "top"):
+                        raise ValueError(f"QuadraticDragBC on the {side} of {fname}: it is offered on the bottom and top of u and v")
+                    if grid.topo[2] != Bounded:
+                        raise ValueError(f"QuadraticDragBC on the {side} of {fname}: z is not Bounded")
+                    dr = td.drag[names.index(fname)][_SIDES[side] - L.BOTTOM]
+                    dr.present, dr.cd, dr.u_background, dr.v_background = 1, bc.cd, bc.u_background, bc.v_background
+                else:
+                    fill(d.bcs[names.index(fname)], side, bc)
         self.desc = d
         self.h = C.c_void_p()
         # forcing: {field: one of Relaxation / Forcing / function of (x, y, z, t), or a tuple of them}
@@ -621,7 +722,8 @@ class NonhydrostaticModel:
         self.background_fields = self._regularize_background(background_fields, names)
         self.background_uploads = 0        # column-table sets sent so far (one per stage slot whose contents changed)
         self._background_sent = [None] * 3
-        if self.forcing or self.background_fields:
+        tilted = bool(td.has_gravity_vector or td.coriolis_cartesian or any(td.drag[f][s].present for f in range(2) for s in range(2)))
+        if self.forcing or self.background_fields or tilted:
             fd = L.ForcingDesc()
             for n, parts in self.forcing.items():
                 bit = 1 << names.index(n)
@@ -644,7 +746,10 @@ class NonhydrostaticModel:
                         raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
                     sd.Pr[i] = smag.Pr_of(n)
             features = L.FEATURE_STOKES_DRIFT if stokes_drift is not None else 0
-            if self.background_fields:
+            if tilted:
+                check(self.lib.ocn_model_create_tilted(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
+                                                       C.byref(fd), C.byref(bd), C.byref(td), C.byref(self.h)), self.ctx.h)
+            elif self.background_fields:
                 check(self.lib.ocn_model_create_background(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
                                                            C.byref(fd), C.byref(bd), C.byref(self.h)), self.ctx.h)
             else:

@@ -879,11 +879,47 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with, ocn_model_create_forced and
-// ocn_model_create_background share this body
+// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with, ocn_model_create_forced,
+// ocn_model_create_background and ocn_model_create_tilted share this body
 static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes,
-                        const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
+                        const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
+                        ocn_model** out) {
   ocn_ctx* ctx = g->ctx;
+  if (tilted) {
+    if (g->dist || g->dist_y || ctx->nranks > 1) {
+      ocn_set_error(ctx, "tilted gravity, Cartesian Coriolis and quadratic drag on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) are not supported");
+      return OCN_EUNSUPPORTED;
+    }
+    if (tilted->has_gravity_vector && desc->buoyancy == OCN_BUOYANCY_NONE) {
+      ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs a buoyancy model (desc->buoyancy is OCN_BUOYANCY_NONE)");
+      return OCN_EINVAL;
+    }
+    if (tilted->has_gravity_vector && desc->n_tracers >= 0 && desc->n_tracers <= OCN_MAX_TRACERS) {
+      auto ok = [&](int i) { return i >= 0 && i < desc->n_tracers; };
+      if ((desc->buoyancy == OCN_BUOYANCY_TRACER && !ok(desc->b_index)) ||
+          (desc->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(desc->T_index) && ok(desc->S_index)))) {
+        ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs the buoyancy model's tracers");
+        return OCN_EINVAL;
+      }
+    }
+    if (tilted->coriolis_cartesian && desc->coriolis_fplane) {
+      ocn_set_error(ctx, "ocn_model_create_tilted: Cartesian Coriolis together with desc->coriolis_fplane (a model has one rotation)");
+      return OCN_EINVAL;
+    }
+    for (int f = 0; f < 2; ++f)
+      for (int sd = 0; sd < 2; ++sd) {
+        if (!tilted->drag[f][sd].present) continue;
+        if (g->topo[2] != OCN_BOUNDED) {
+          ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, but z is not Bounded", sd ? "top" : "bottom", f ? "v" : "u");
+          return OCN_EINVAL;
+        }
+        if (desc->bcs[f][OCN_BOTTOM + sd].kind != OCN_BC_DEFAULT) {
+          ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, which already has a boundary condition", sd ? "top" : "bottom",
+                        f ? "v" : "u");
+          return OCN_EINVAL;
+        }
+      }
+  }
   const uint32_t bcol = background ? background->column_members : 0u, bfld = background ? background->field_members : 0u;
   if ((bcol | bfld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((bcol | bfld) >> (3 + desc->n_tracers)) != 0)) {
     ocn_set_error(ctx, "ocn_model_create_background: member masks 0x%x / 0x%x name members beyond u, v, w and the model's %d tracers", bcol, bfld,
@@ -968,6 +1004,12 @@ static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smago
     m->smag_Cb = smag->Cb;
     for (int t = 0; t < m->nt; ++t) m->smag_rPr[t] = 1.0 / smag->Pr[t];
   }
+  if (tilted) {
+    m->tl = *tilted;
+    m->tilt_terms = tilted->has_gravity_vector || tilted->coriolis_cartesian;
+    for (int f = 0; f < 2; ++f)
+      for (int sd = 0; sd < 2; ++sd) m->drag_any = m->drag_any || tilted->drag[f][sd].present;
+  }
   m->gd = g->dev;
   m->gd.nb = buffer[desc->advection];
   int rc = 0;
@@ -1037,6 +1079,10 @@ static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smago
       fld->bc[s] = bd;
     }
   }
+  // a quadratic drag is the Flux condition of its side: the halo fill treats it as one, k_drag_flux adds the flux to G^n
+  for (int f = 0; f < 2; ++f)
+    for (int sd = 0; sd < 2; ++sd)
+      if (m->tl.drag[f][sd].present) (f == 0 ? m->u : m->v).bc[OCN_BOTTOM + sd] = BCdev{OCN_BC_FLUX, 0.0, nullptr};
   if (g->dist && hipMalloc((void**)&m->phi_below, (size_t)g->N[0] * g->N[1] * sizeof(double)) != hipSuccess) {
     ocn_model_destroy(m);
     return OCN_ENOMEM;
@@ -1142,7 +1188,7 @@ extern "C" {
 int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
   if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-  return model_create(g, desc, nullptr, false, nullptr, nullptr, out);
+  return model_create(g, desc, nullptr, false, nullptr, nullptr, nullptr, out);
 }
 
 int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
@@ -1160,7 +1206,16 @@ int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_s
 
 int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
                                 const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
+  return ocn_model_create_tilted(g, desc, smag, features, forcing, background, nullptr, out);
+}
+
+int ocn_model_create_tilted(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
+                            ocn_model** out) {
   if (!g || !desc || !out) return OCN_EINVAL;
+  if (tilted && !tilted->has_gravity_vector && !tilted->coriolis_cartesian && !tilted->drag[0][0].present && !tilted->drag[0][1].present &&
+      !tilted->drag[1][0].present && !tilted->drag[1][1].present)
+    tilted = nullptr;
   if (forcing && !(forcing->column_fields | forcing->field_fields)) forcing = nullptr;
   if (background && !(background->column_members | background->field_members)) background = nullptr;
   if (features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
@@ -1170,7 +1225,7 @@ int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const o
   const bool stokes = (features & OCN_FEATURE_STOKES_DRIFT) != 0;
   if (!smag) {
     if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-    return model_create(g, desc, nullptr, stokes, forcing, background, out);
+    return model_create(g, desc, nullptr, stokes, forcing, background, tilted, out);
   }
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
@@ -1203,7 +1258,7 @@ int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const o
     ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
     return OCN_EINVAL;
   }
-  return model_create(g, desc, smag, stokes, forcing, background, out);
+  return model_create(g, desc, smag, stokes, forcing, background, tilted, out);
 }
 
 int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,

@@ -545,8 +545,15 @@ struct RestArgs {
 // start in mid-column) issued at the top of the level, ahead of the stresses; 2: the field form as well, its values read at the
 // cell's own byte offset (stencils.h force_at_o).  The two are separate instantiations because the field form's nine array
 // pointers cost scalar registers that the column form alone does not need.
-template <int BX, int BY, bool ZB, bool NU0, bool STOKES = false, int FORCE = 0>   // NU0: a.nu0 is added to the eddy viscosity
-__global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
+// TILT: a gravity unit vector (t.tilt) and / or ConstantCartesianCoriolis (t.cart), selected by those uniform flags; the plain
+// instantiations never look at t.  Tilted gravity: gx b, gy b join the pointwise terms of level k with b of the cell's own byte
+// offset (the tracers are not in the slab), loaded next to pH.  Cartesian rotation: the fz parts are pointwise terms of level k
+// (the f-plane's slab reads); the parts with w follow the STOKES pattern -- I_x w, I_y w of the level below are carried (shared
+// with STOKES), G_u, G_v of level k-1 are completed when face k is in the slab -- and G_w of face k takes C = fx I_y v - fy I_x u of
+// level k-1 from a register.  The outer two-point average is distributed over the difference (I_x(fy I_z w) = fy I_z(I_x w)): a
+// rounding of the term away from the reference's association, not a reordering of anything else.
+template <int BX, int BY, bool ZB, bool NU0, bool STOKES = false, int FORCE = 0, bool TILT = false>   // NU0: a.nu0 is added to the eddy viscosity
+__global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a, TiltDev t) {
   const double nu0 = NU0 ? a.nu0 : 0.0;
   constexpr int T = BX * BY, NR = BY + 1, SX = BX + 6;      // rows j0-1 .. j0+BY-1; columns -3 .. Nx+2 (the parent row)
   constexpr int WV = BX < OCN_WAVE ? BX : OCN_WAVE, NW = BX / WV, NWV = T / WV;
@@ -604,11 +611,14 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
     double ncp = amd ? (NU0 ? ldo(a.nue, cb) + nu0 : ldo(a.nue, cb)) : a.nu, nwp = amd ? (NU0 ? ldo(a.nue, cb - sxb) + nu0 : ldo(a.nue, cb - sxb)) : a.nu, nsp = amd ? (NU0 ? ldo(a.nue, cb - syb) + nu0 : ldo(a.nue, cb - syb)) : a.nu;
     double hu = 0, hv = 0, hw = 0, bu = 0, bv = 0, bw = 0;
     double wxp = 0, wyp = 0, uxp = 0, vyp = 0;       // STOKES: I_x w, I_y w, I_x u, I_y v of the level below
-    if (STOKES) {
+    double ccp = 0;                                   // TILT: fx I_y v - fy I_x u of the level below
+    const bool cart = TILT && t.cart != 0, tilt = TILT && t.tilt != 0;
+    if (STOKES || cart) {
       wxp = 0.5 * (ldo(a.w, cb - sxb) + wp);
       wyp = 0.5 * (ldo(a.w, cb - syb) + wp);
       uxp = 0.5 * (up + ldo(a.u, cb + sxb));
       vyp = 0.5 * (vp + ldo(a.v, cb + syb));
+      if (cart) ccp = t.fx * vyp - t.fy * uxp;
     }
     __syncthreads();
     dma(k0, 0);
@@ -634,6 +644,8 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
         pw = ldo(a.pH, c - sxb);
         ps = ldo(a.pH, c - syb);
       }
+      double bc = 0;                                  // TILT: the buoyancy of this cell
+      if (tilt && full && !last) bc = t.buoyancy == OCN_BUOYANCY_TRACER ? ldo(t.b, c) : t.g * (t.alpha * ldo(t.T, c) - t.beta * ldo(t.S, c));
       if (full && k > k0) {                           // complete level k-1's horizontal part with the north / x-edge values
         const double* fyp = fyb + (kb ^ 1) * 3 * T;
         const double rdy2 = rdy + rdy, rdx2 = rdx + rdx;       // the stress divergence carries a factor 2
@@ -670,7 +682,7 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
         fyn[2 * T + tid] = t23;
       }
       double wx = 0, wy = 0, ux = 0, vy = 0;
-      if (STOKES && full) {                           // row ty + 1 of the slab exists for output rows only
+      if ((STOKES || cart) && full) {                 // row ty + 1 of the slab exists for output rows only
         wx = 0.5 * (RS(2, 0, -1) + wc);
         wy = 0.5 * (RS(2, -1, 0) + wc);
         ux = 0.5 * (uc + RS(0, 0, 1));
@@ -697,6 +709,10 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
             hu += 0.5 * (wxp + wx) * OCN_SLOAD(sk) + OCN_SLOAD(sk + 4 * g.Nz);
             hv += 0.5 * (wyp + wy) * OCN_SLOAD(sk + g.Nz) + OCN_SLOAD(sk + 5 * g.Nz);
           }
+          if (cart) {
+            hu -= t.fy * (0.5 * (wxp + wx));
+            hv += t.fx * (0.5 * (wyp + wy));
+          }
           sto(a.gu, cm1, hu + 2.0 * ((t13 - bu) * rzc));
           sto(a.gv, cm1, hv + 2.0 * ((t23 - bv) * rzc));
           sto(a.gw, cm1, hw + 2.0 * ((t33 - bw) * rzfm));   // w at face k-1: tau33 at centre k-1 (here) minus centre k-2 (carried)
@@ -708,6 +724,14 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
           if (a.coriolis) {
             cu = a.f * (0.5 * (0.5 * (RS(1, 0, -1) + vc) + 0.5 * (RS(1, 1, -1) + RS(1, 1, 0))));
             cv = -a.f * (0.5 * (0.5 * (RS(0, -1, 0) + RS(0, -1, 1)) + 0.5 * (uc + RS(0, 0, 1))));
+          }
+          if (cart) {
+            cu += t.fz * (0.5 * (0.5 * (RS(1, 0, -1) + RS(1, 1, -1)) + vy));
+            cv -= t.fz * (0.5 * (0.5 * (RS(0, -1, 0) + RS(0, -1, 1)) + ux));
+          }
+          if (tilt) {
+            cu += t.gx * bc;
+            cv += t.gy * bc;
           }
           if (a.pH) {
             cu -= (p0 - pw) * rdx;
@@ -725,6 +749,11 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
           hv = cv + 2.0 * fma(xedge ? -t12 : e1 - t12, rdx, -t22 * rdy);
           hw = 2.0 * fma(xedge ? -t13 : e2 - t13, rdx, -t23 * rdy);
           if (STOKES) hw -= 0.5 * (uxp + ux) * OCN_SLOAD(a.sk + 2 * g.Nz + k) + 0.5 * (vyp + vy) * OCN_SLOAD(a.sk + 3 * g.Nz + k);
+          if (cart) {
+            const double cc = t.fx * vy - t.fy * ux;
+            hw -= 0.5 * (ccp + cc);
+            ccp = cc;
+          }
           if (FORCE) hw += csw * (ctw - wc) + cfw;
           if (FORCE == 2 && force_any(a.fo[2])) hw += force_at_o(a.fo[2], k, g.Nz, c, wc);
           bu = t13;
@@ -734,7 +763,7 @@ __global__ void __launch_bounds__(BX* BY) k_rest4(GridDev g, RestArgs a) {
       }
       up = uc; vp = vc; wp = wc;
       ncp = nc; nwp = nw; nsp = ns;
-      if (STOKES) { wxp = wx; wyp = wy; uxp = ux; vyp = vy; }
+      if (STOKES || cart) { wxp = wx; wyp = wy; uxp = ux; vyp = vy; }
     }
   }
 #undef RS
@@ -1099,7 +1128,7 @@ static bool fused_available_but_for_stokes(const ocn_model* m) {
   if (!g->z_regular) return false;
   // ScalarDiffusivity (constant nu, kappa) rides in the face fluxes of the fused kernels; other closures, Coriolis and
   // buoyancy take the general path
-  if (m->d.closure == OCN_CLOSURE_AMD || m->d.closure == OCN_CLOSURE_SMAG || m->d.coriolis_fplane || m->d.buoyancy != OCN_BUOYANCY_NONE) return false;
+  if (m->d.closure == OCN_CLOSURE_AMD || m->d.closure == OCN_CLOSURE_SMAG || m->d.coriolis_fplane || m->tl.coriolis_cartesian || m->d.buoyancy != OCN_BUOYANCY_NONE) return false;
   if (tiled_blocker(m)) return false;
   if (getenv("OCNHIP_NO_FUSED")) return false;   // model creation only
   return true;
@@ -1156,6 +1185,16 @@ void fused_describe(const ocn_model* m, char* buf, size_t n) {
              !m->stokes && !model_forced(m) && fused_available_but_for_stokes(m) ? "not the all-in-one periodic path: " : "",
              mom ? "k_bg_uvw" : "", mom && trc ? " and " : "", trc ? "k_bg_c" : "", form,
              m->d.advection == ADV_NONE ? ", which launch nothing without an advection scheme" : "");
+  }
+  if (m->tilt_terms || m->drag_any) {   // which kernels add the tilted-gravity / Cartesian-rotation terms and the drag
+    size_t l = strlen(buf);
+    if (m->tilt_terms)
+      snprintf(buf + l, n - l, "; %s%s%s terms are served by %s%s", m->tl.has_gravity_vector ? "tilted gravity" : "",
+               m->tl.has_gravity_vector && m->tl.coriolis_cartesian ? " and " : "", m->tl.coriolis_cartesian ? "Cartesian Coriolis" : "",
+               m->bz_fast && rest4_ok(m) ? "k_rest4 (TILT)" : "the general kernel (k_tend_uvw, TILT)",
+               m->tl.has_gravity_vector ? (m->gd.Nz >= 64 && m->gd.Nz <= 256 ? " and k_hydrostatic_seg (gz b)" : " and k_hydrostatic (gz b)") : "");
+    l = strlen(buf);
+    if (m->drag_any) snprintf(buf + l, n - l, "; quadratic drag is served by k_drag_flux");
   }
   if (m->d.closure == OCN_CLOSURE_SMAG) {
     const size_t l = strlen(buf);
@@ -1454,7 +1493,9 @@ bool launch_rest4(ocn_model* m) {
   const dim3 blk(bx, by, 1), grd(nseg, 1, 1);
   hipStream_t s = m->ctx->stream;
   const bool zb = m->g->topo[2] == OCN_BOUNDED;
-#define REST4F(BXV, BYV, N0, SK, FO) { if (zb) ocn_launch_sync(k_rest4<BXV, BYV, true, N0, SK, FO>, grd, blk, s, gd, a); else ocn_launch_sync(k_rest4<BXV, BYV, false, N0, SK, FO>, grd, blk, s, gd, a); }
+  const TiltDev td = tilt_of(m, false);
+#define REST4T(BXV, BYV, ZBV, N0, SK, FO) { if (m->tilt_terms) ocn_launch_sync(k_rest4<BXV, BYV, ZBV, N0, SK, FO, true>, grd, blk, s, gd, a, td); else ocn_launch_sync(k_rest4<BXV, BYV, ZBV, N0, SK, FO, false>, grd, blk, s, gd, a, td); }
+#define REST4F(BXV, BYV, N0, SK, FO) { if (zb) REST4T(BXV, BYV, true, N0, SK, FO) else REST4T(BXV, BYV, false, N0, SK, FO) }
 #define REST4S(BXV, BYV, N0, SK) { if (forced == 2) REST4F(BXV, BYV, N0, SK, 2) else if (forced) REST4F(BXV, BYV, N0, SK, 1) else REST4F(BXV, BYV, N0, SK, 0) }
 #define REST4N(BXV, BYV, N0) { if (a.sk) REST4S(BXV, BYV, N0, true) else REST4S(BXV, BYV, N0, false) }
 #define REST4(BXV, BYV) { if (a.nu0 != 0.0) REST4N(BXV, BYV, true) else REST4N(BXV, BYV, false) }
@@ -1466,6 +1507,7 @@ bool launch_rest4(ocn_model* m) {
 #undef REST4N
 #undef REST4S
 #undef REST4F
+#undef REST4T
   return true;
 }
 

@@ -1,5 +1,6 @@
 // internal.h -- host-side objects behind the opaque handles of include/ocnhip.h
 #pragma once
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -187,6 +188,11 @@ struct ocn_model {
   double* bg_stage = nullptr;      // host staging of the same shape
   hipEvent_t bg_ev[3][OCN_NF] = {};   // recorded behind each (slot, member) upload
   double* bg_arr[OCN_NF] = {};     // field form
+  // Tilted gravity, ConstantCartesianCoriolis, quadratic drag (ocn_model_create_tilted): the descriptor as given.  tilt_terms: a
+  // gravity vector or a Cartesian rotation is set, so the TILT instantiations of k_tend_uvw / k_rest4 (and, with a gravity vector,
+  // of k_hydrostatic*) serve the model; drag_any: k_drag_flux launches behind the flux-boundary kernels.
+  ocn_tilted_desc tl = {};
+  bool tilt_terms = false, drag_any = false;
   bool graph_off = false;    // a capture failed: this model steps launch by launch from then on
   int64_t graph_replays = 0;
 };
@@ -222,6 +228,29 @@ inline ForceDev force_of(const ocn_model* m, int f, bool interior) {
     fo.ff = m->force_arr[f][2] ? m->force_arr[f][2] + org : nullptr;
   }
   return fo;
+}
+
+// What the TILT instantiations read, the trailing argument of k_tend_uvw / k_rest4 / k_hydrostatic* (the plain instantiations never
+// look at it): the gravity unit vector and the buoyancy model's tracers (tilt), the rotation vector (cart).  Wave-uniform.
+struct TiltDev {
+  double gx, gy, gz, fx, fy, fz;
+  int tilt, cart, buoyancy;
+  double g, alpha, beta;
+  const double *b, *T, *S;   // interior pointers (general kernels) or parent bases (k_rest4)
+};
+inline TiltDev tilt_of(const ocn_model* m, bool interior) {
+  TiltDev t;
+  memset(&t, 0, sizeof(t));
+  if (!m->tilt_terms) return t;
+  t.tilt = m->tl.has_gravity_vector;
+  t.cart = m->tl.coriolis_cartesian;
+  t.gx = m->tl.gx; t.gy = m->tl.gy; t.gz = m->tl.gz;
+  t.fx = m->tl.fx; t.fy = m->tl.fy; t.fz = m->tl.fz;
+  t.buoyancy = m->d.buoyancy;
+  t.g = m->d.g; t.alpha = m->d.alpha; t.beta = m->d.beta;
+  auto base = [&](int idx) -> const double* { return idx < 0 ? nullptr : interior ? m->tr[idx].interior() : m->tr[idx].d; };
+  if (t.tilt) { t.b = base(m->d.b_index); t.T = base(m->d.T_index); t.S = base(m->d.S_index); }
+  return t;
 }
 
 inline bool model_background(const ocn_model* m) { return (m->bg_col | m->bg_fld) != 0; }

@@ -53,10 +53,12 @@ OCN_DEVFN double nu_cff(const Phys& ph, long p, long sy, long sz) {
 }
 
 // FORCE: the model has forcing on u, v or w (ph.fo); the instantiations of unforced models never look at it
-template <int ADV, bool WALLS, bool FORCE = false>
+// TILT: a gravity unit vector and / or a Cartesian rotation vector (td, selected by its uniform flags); every other instantiation
+// never looks at td.  TILT models use the FORCE = true instantiation, which finds out at run time that nothing is forced.
+template <int ADV, bool WALLS, bool FORCE = false, bool TILT = false>
 __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, const double* __restrict__ v,
                            const double* __restrict__ w, double* __restrict__ Gu, double* __restrict__ Gv,
-                           double* __restrict__ Gw) {
+                           double* __restrict__ Gw, TiltDev td) {
   int i, j;
   ocn_cell_ij(i, j);
   const int k = blockIdx.z;   // one level per workgroup: k is wave-uniform, so spacings are scalar loads and 1/dz is computed once per wave
@@ -120,6 +122,23 @@ __global__ void k_tend_uvw(GridDev g, Phys ph, const double* __restrict__ u, con
   if (ph.coriolis) {
     gu += ph.f * (0.5 * (0.5 * (v[c - 1] + v[c]) + 0.5 * (v[c - 1 + sy] + v[c + sy])));
     gv -= ph.f * (0.5 * (0.5 * (u[c - sy] + u[c + 1 - sy]) + 0.5 * (u[c] + u[c + 1])));
+  }
+  // ---- ConstantCartesianCoriolis (constant_cartesian_coriolis.jl:68-79): the two-point average of a centred difference of
+  // two-point averages, all in the reference's association; a Flat z averages nothing ----
+  if (TILT && td.cart) {
+    const long szz = zf ? 0 : sz;
+    auto A = [&](long p) { return td.fy * (0.5 * (w[p] + w[p + szz])) - td.fz * (0.5 * (v[p] + v[p + sy])); };
+    auto Bc = [&](long p) { return td.fz * (0.5 * (u[p] + u[p + 1])) - td.fx * (0.5 * (w[p] + w[p + szz])); };
+    auto Cc = [&](long p) { return td.fx * (0.5 * (v[p] + v[p + sy])) - td.fy * (0.5 * (u[p] + u[p + 1])); };
+    gu -= 0.5 * (A(c - 1) + A(c));
+    gv -= 0.5 * (Bc(c - sy) + Bc(c));
+    gw -= 0.5 * (Cc(c - szz) + Cc(c));
+  }
+  // ---- tilted gravity (g_dot_b.jl:1-2): the buoyancy of the centre with the velocity point's own index ----
+  if (TILT && td.tilt) {
+    const double bc = td.buoyancy == OCN_BUOYANCY_TRACER ? td.b[c] : td.g * (td.alpha * td.T[c] - td.beta * td.S[c]);
+    gu += td.gx * bc;
+    gv += td.gy * bc;
   }
   // ---- hydrostatic pressure gradient (nonhydrostatic_tendency_kernel_functions.jl:10-15) ----
   if (ph.pH) {
@@ -238,6 +257,37 @@ __global__ void k_apply_flux(GridDev g, double* __restrict__ G, int dim, int zlo
   }
 }
 
+// QuadraticDragBC on the bottom / top of u (comp 0) or v (comp 1): the flux ((-cd) sqrt(U U + V V)) U (or V) with U = u + U_inf,
+// V = v + V_inf at the field's own location and the boundary-adjacent level -- the field's own value, the other component by
+// I_xy with y outside (interpolation_utils.jl:99-109) -- added like every z flux: G[1] += flux / dz, G[Nz] -= flux / dz.
+// Reads the fields themselves: nothing per step comes from the host, so the launch is capturable.
+__global__ void k_drag_flux(GridDev g, double* __restrict__ G, const double* __restrict__ u, const double* __restrict__ v, int comp,
+                            ocn_quadratic_drag lo, ocn_quadratic_drag hi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  if (i >= g.Nx || j >= g.Ny) return;
+  const long sy = g.sy;
+  auto flux = [&](long p, const ocn_quadratic_drag& d) -> double {
+    double U, V;
+    if (comp == 0) {
+      U = u[p];
+      V = 0.5 * (0.5 * (v[p - 1] + v[p]) + 0.5 * (v[p - 1 + sy] + v[p + sy]));     // I_xy^{fc}
+    } else {
+      U = 0.5 * (0.5 * (u[p - sy] + u[p + 1 - sy]) + 0.5 * (u[p] + u[p + 1]));     // I_xy^{cf}
+      V = v[p];
+    }
+    U += d.u_background;
+    V += d.v_background;
+    return ((-d.cd) * sqrt(U * U + V * V)) * (comp == 0 ? U : V);
+  };
+  const long c = i + j * sy;
+  if (lo.present) G[c] += flux(c, lo) * (1.0 / g_dzc(g, 0));
+  if (hi.present) {
+    const long p = c + (long)(g.Nz - 1) * g.sz;
+    G[p] -= flux(p, hi) * (1.0 / g_dzc(g, g.Nz - 1));
+  }
+}
+
 // G^n of tracer t before the boundary fluxes are added, when everything else comes from the tiled tracer kernel: zero where
 // that kernel will read it -- the whole array with walls in x / y, else the first and last level only (fused.hip rest_shell)
 static void tracer_gn_clear(ocn_model* m, int t) {
@@ -270,6 +320,7 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
   ph.sk = stokes_slot(m);
   for (int f = 0; f < 3; ++f) ph.fo[f] = force_of(m, f, true);
   const bool forced_uvw = force_any(ph.fo[0]) || force_any(ph.fo[1]) || force_any(ph.fo[2]);
+  const TiltDev td = tilt_of(m, true);
   static const dim3 b = tuned_block("OCNHIP_TEND_BLOCK", dim3(64, 4, 1));
   const dim3 gr = grid3(g, b);
   const double *u = m->u.interior(), *v = m->v.interior(), *w = m->w.interior();
@@ -280,8 +331,9 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
              (const double*)(smag ? m->nu_e.interior() : m->kappa_e[t].present ? m->kappa_e[t].interior() : nullptr), \
              smag ? m->smag_rPr[t] : 1.0, m->d.closure, force_of(m, 3 + t, true), m->Gn[3 + t].interior());
 #define TEND_TRACER(A, W, t) if (force_any(force_of(m, 3 + t, true))) { TEND_TRACER_F(A, W, t, true) } else { TEND_TRACER_F(A, W, t, false) }
-#define TEND_UVW(A, W) { if (forced_uvw) ocn_launch(k_tend_uvw<A, W, true>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); \
-                         else ocn_launch(k_tend_uvw<A, W, false>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw); }
+#define TEND_UVW(A, W) { if (m->tilt_terms) ocn_launch(k_tend_uvw<A, W, true, true>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw, td); \
+                         else if (forced_uvw) ocn_launch(k_tend_uvw<A, W, true>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw, td); \
+                         else ocn_launch(k_tend_uvw<A, W, false>, gr, b, s, g, ph, u, v, w, Gu, Gv, Gw, td); }
 #define TEND_LAUNCH(A, W)                                                       \
   if (skip_momentum_advection) { if (!launch_rest4(m)) TEND_UVW(ADV_NONE, W) }  \
   else TEND_UVW(A, W)                                                           \
@@ -328,6 +380,12 @@ void launch_tendencies(ocn_model* m, bool skip_momentum_advection, bool skip_tra
       if (!nh) h_.kind = OCN_BC_NOFLUX;
       ocn_launch(k_apply_flux, g2, b2, s, g, m->Gn[f].interior(), dim, fld->loc[2], l_, h_);
     }
+  }
+  if (m->drag_any) {
+    dim3 b2(64, 4, 1), g2((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
+    for (int f = 0; f < 2; ++f)
+      if (m->tl.drag[f][0].present || m->tl.drag[f][1].present)
+        ocn_launch(k_drag_flux, g2, b2, s, g, m->Gn[f].interior(), u, v, f, m->tl.drag[f][0], m->tl.drag[f][1]);
   }
   // BackgroundFields: both advection terms join G^n in launches of their own (background.hip), after the kernels above (or
   // k_rest4) wrote it and before k_step / k_tend4 / k_tracer_step3<REST> consume it
@@ -633,15 +691,18 @@ void launch_pcorrect(ocn_model* m, double dt) {
 }
 
 // ---- hydrostatic pressure anomaly (update_hydrostatic_pressure.jl:10-18) ---------------------------------------
+// GZ: a gravity unit vector; every level's buoyancy is multiplied by its z component gz before the two-point average, I_z(gz b)
+// (update_hydrostatic_pressure.jl:13,16 with z_dot_g_b).  The plain instantiation never looks at gz.
+template <bool GZ>
 __global__ void k_hydrostatic(GridDev g, Phys ph, const double* __restrict__ b0, const double* __restrict__ T,
-                              const double* __restrict__ S, double* __restrict__ pH) {
+                              const double* __restrict__ S, double* __restrict__ pH, double gz) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   if (i >= g.Nx || j >= g.Ny) return;
   const long c = i + j * g.sy, sz = g.sz;
   auto bz = [&](long p) -> double {
-    if (ph.buoyancy == OCN_BUOYANCY_TRACER) return b0[p];
-    if (ph.buoyancy == OCN_BUOYANCY_LINEAR_TS) return ph.g * (ph.alpha * T[p] - ph.beta * S[p]);
+    if (ph.buoyancy == OCN_BUOYANCY_TRACER) return GZ ? gz * b0[p] : b0[p];
+    if (ph.buoyancy == OCN_BUOYANCY_LINEAR_TS) return GZ ? gz * (ph.g * (ph.alpha * T[p] - ph.beta * S[p])) : ph.g * (ph.alpha * T[p] - ph.beta * S[p]);
     return 0.0;
   };
   const int Nz = g.Nz;
@@ -671,9 +732,9 @@ __global__ void k_hydrostatic(GridDev g, Phys ph, const double* __restrict__ b0,
 // before it stores.  The serial kernel keeps one wave per SIMD busy for 128 dependent steps (2.4 TB/s at 256 x 256 x 128); this
 // one has SEG times the waves and 1 / SEG of the chain.  The association differs from the reference's top-to-bottom sum by the
 // one addition of the carry (a few ulp of pHY'): used for columns of 64 levels or more, the serial kernel below that.
-template <int SEG, int LPS>
+template <int SEG, int LPS, bool GZ>
 __global__ void __launch_bounds__(64 * SEG) k_hydrostatic_seg(GridDev g, Phys ph, const double* __restrict__ b0, const double* __restrict__ T,
-                                                               const double* __restrict__ S, double* __restrict__ pH) {
+                                                               const double* __restrict__ S, double* __restrict__ pH, double gz) {
   OCN_SHARED double tot[SEG][64];
   const int tx = threadIdx.x, s = threadIdx.y;                 // s = 0: the top segment
   const int col = blockIdx.x * 64 + tx;                        // flattened (i, j): i fastest
@@ -682,8 +743,8 @@ __global__ void __launch_bounds__(64 * SEG) k_hydrostatic_seg(GridDev g, Phys ph
   const int j = ok ? col / g.Nx : 0, i = ok ? col - j * g.Nx : 0;
   const long c = i + (long)j * g.sy, sz = g.sz;
   auto bz = [&](long p) -> double {
-    if (ph.buoyancy == OCN_BUOYANCY_TRACER) return b0[p];
-    if (ph.buoyancy == OCN_BUOYANCY_LINEAR_TS) return ph.g * (ph.alpha * T[p] - ph.beta * S[p]);
+    if (ph.buoyancy == OCN_BUOYANCY_TRACER) return GZ ? gz * b0[p] : b0[p];
+    if (ph.buoyancy == OCN_BUOYANCY_LINEAR_TS) return GZ ? gz * (ph.g * (ph.alpha * T[p] - ph.beta * S[p])) : ph.g * (ph.alpha * T[p] - ph.beta * S[p]);
     return 0.0;
   };
   const int Nz = g.Nz;
@@ -727,16 +788,20 @@ void launch_hydrostatic(ocn_model* m) {
   const double* b0 = m->d.b_index >= 0 ? m->tr[m->d.b_index].interior() : nullptr;
   const double* T = m->d.T_index >= 0 ? m->tr[m->d.T_index].interior() : nullptr;
   const double* S = m->d.S_index >= 0 ? m->tr[m->d.S_index].interior() : nullptr;
+  const bool tilted = m->tl.has_gravity_vector != 0;   // Buoyancy(model, gravity_unit_vector): pHY' from gz b
+  const double gz = m->tl.gz;
   if (g.Nz >= 64 && g.Nz <= 8 * 32) {   // segmented form: 8 segments of 8 / 16 / 32 levels
     const int ncol = g.Nx * g.Ny;
     dim3 bs(64, 8, 1), gs((ncol + 63) / 64, 1, 1);
-    if (g.Nz <= 64) ocn_launch_sync(k_hydrostatic_seg<8, 8>, gs, bs, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior());
-    else if (g.Nz <= 128) ocn_launch_sync(k_hydrostatic_seg<8, 16>, gs, bs, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior());
-    else ocn_launch_sync(k_hydrostatic_seg<8, 32>, gs, bs, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior());
+#define HSEG(LPS) { if (tilted) ocn_launch_sync(k_hydrostatic_seg<8, LPS, true>, gs, bs, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior(), gz); \
+                    else ocn_launch_sync(k_hydrostatic_seg<8, LPS, false>, gs, bs, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior(), gz); }
+    if (g.Nz <= 64) HSEG(8) else if (g.Nz <= 128) HSEG(16) else HSEG(32)
+#undef HSEG
     return;
   }
   dim3 b(64, 4, 1), gr((g.Nx + 63) / 64, (g.Ny + 3) / 4, 1);
-  ocn_launch(k_hydrostatic, gr, b, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior());
+  if (tilted) ocn_launch(k_hydrostatic<true>, gr, b, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior(), gz);
+  else ocn_launch(k_hydrostatic<false>, gr, b, m->ctx->stream, g, ph, b0, T, S, m->pHY.interior(), gz);
 }
 
 // ---- compact (Nx,Ny,Nz) array -> field interior (copy_real_component!, fft_based_poisson_solver.jl:122-125) --

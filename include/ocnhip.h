@@ -279,6 +279,41 @@ int ocn_model_set_background_column(ocn_model* m, int member, int stage, const d
  * contents (the device address stays); callable between steps.  OCN_ESTATE: the member was not declared in field_members;
  * OCN_EINVAL: member out of range, array NULL, (tx, ty, tz) != the parent's totals. */
 int ocn_model_set_background_field(ocn_model* m, int member, const double* array, int tx, int ty, int tz);
+/* Tilted gravity, ConstantCartesianCoriolis and quadratic drag -- what examples/tilted_bottom_boundary_layer.jl needs on top of
+ * everything above (BuoyancyModels/buoyancy.jl, g_dot_b.jl, update_hydrostatic_pressure.jl:13,16,
+ * nonhydrostatic_tendency_kernel_functions.jl:70,127, Coriolis/constant_cartesian_coriolis.jl:68-79).
+ *   has_gravity_vector: Buoyancy(model, gravity_unit_vector = (gx, gy, gz)).  With b the buoyancy of desc->buoyancy at the centre
+ *     that has the velocity point's own index (not interpolated, as in the reference): G_u += gx b, G_v += gy b, and pHY' is
+ *     integrated from I_z(gz b).  Closures that use d_z b keep the model's plain z gradient.  (0, 0, 1) takes this path too and
+ *     changes no bit; the caller validates the unit length.
+ *   coriolis_cartesian: the rotation vector (fx, fy, fz) with the non-traditional terms,
+ *         G_u -= I_x(fy I_z w - fz I_y v),  G_v -= I_y(fz I_x u - fx I_z w),  G_w -= I_z(fx I_y v - fy I_x u),
+ *     instead of desc->coriolis_fplane (the two are exclusive; FPlane keeps its own association of the averages).
+ *   drag[f][s]: a quadratic drag as the Flux condition of u (f = 0) or v (f = 1) on the bottom (s = 0) or top (s = 1):
+ *         flux = ((-cd) sqrt(U U + V V)) U on u,  ((-cd) sqrt(U U + V V)) V on v,   U = u + u_background, V = v + v_background,
+ *     both at the location of the field that carries the condition (its own value; the other component by I_xy, y outside) and
+ *     at the boundary-adjacent level k = 1 / Nz, halo values as update_state left them.  It enters like every flux:
+ *     G[1] += flux / dz, G[Nz] -= flux / dz.  A function of the model's fields cannot cross this boundary
+ *     (FluxBoundaryCondition(f, field_dependencies = ...)); the example's drag is offered by its parameters instead.
+ * All of it is a creation-time property: it decides kernels (never the all-in-one periodic path; ocn_model_path says which
+ * kernels serve the terms).  tilted == NULL or nothing set: exactly ocn_model_create_background.  OCN_EINVAL: a gravity vector
+ * with desc->buoyancy == OCN_BUOYANCY_NONE; coriolis_cartesian together with desc->coriolis_fplane; a drag on a side that is not
+ * Bounded in z or whose ocn_bc in desc is already set.  OCN_EUNSUPPORTED: a distributed grid (z- or y-slabs, more than one rank,
+ * OCNHIP_FORCE_DIST). */
+typedef struct ocn_quadratic_drag {
+  int32_t present;
+  double cd, u_background, v_background;
+} ocn_quadratic_drag;
+typedef struct ocn_tilted_desc {
+  int32_t has_gravity_vector;
+  double gx, gy, gz;
+  int32_t coriolis_cartesian;
+  double fx, fy, fz;
+  ocn_quadratic_drag drag[2][2];   /* [u, v][bottom, top] */
+} ocn_tilted_desc;
+int ocn_model_create_tilted(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
+                            ocn_model** out);
 void ocn_model_destroy(ocn_model* m);
 /* which kernels serve this model, and if not the fastest ones, why (e.g. "general kernels: parent arrays of 2 GiB or
  * more exceed the tiled kernels' 32-bit byte offsets").  Writes at most n bytes incl. the terminating 0. */

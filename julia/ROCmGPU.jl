@@ -91,6 +91,24 @@ function bc_of(bc, keep)
     return BC(kind, c === nothing ? 0.0 : Float64(c), C_NULL)
 end
 
+# `ocn_tilted_desc` (include/ocnhip.h), field by field: Buoyancy{M, <:Tuple} and ConstantCartesianCoriolis map onto it.  The drag
+# slots ([u, v][bottom, top]: present, cd, u_background, v_background) stay empty here: the reference writes its drag as a
+# ContinuousBoundaryFunction, which cannot cross the C ABI (bc_of refuses it); the library offers it by parameters.
+struct QuadraticDrag; present::Int32; cd::Float64; u_background::Float64; v_background::Float64; end
+struct TiltedDesc
+    has_gravity_vector::Int32; gx::Float64; gy::Float64; gz::Float64
+    coriolis_cartesian::Int32; fx::Float64; fy::Float64; fz::Float64
+    drag::NTuple{2, NTuple{2, QuadraticDrag}}
+end
+function tilted_desc(m)
+    nodrag = ntuple(_ -> ntuple(_ -> QuadraticDrag(0, 0.0, 0.0, 0.0), 2), 2)
+    ĝ = m.buoyancy === nothing ? nothing : m.buoyancy.gravity_unit_vector
+    g = ĝ isa Tuple ? (Int32(1), Float64.(ĝ)...) : (Int32(0), 0.0, 0.0, 0.0)              # ZDirection: the plain kernels
+    c = m.coriolis
+    f = c isa ConstantCartesianCoriolis ? (Int32(1), Float64(c.fx), Float64(c.fy), Float64(c.fz)) : (Int32(0), 0.0, 0.0, 0.0)
+    return TiltedDesc(g..., f..., nodrag)
+end
+
 function ocn_model(arch::ROCmGPU, gridh, m)                                             # m: the fields NonhydrostaticModel(...) assembled
     bplan = background_plan(m)                                                          # which members exist and in which form
     fplan = forcing_plan(m)                                                             # refuses what cannot be tabulated, by name
@@ -117,13 +135,20 @@ function ocn_model(arch::ROCmGPU, gridh, m)                                     
     fields = (m.velocities.u, m.velocities.v, m.velocities.w, values(m.tracers)...)
     desc = ModelDesc(adv_code(m.advection), m.timestepper isa RungeKutta3TimeStepper ? 1 : 0,
                      m.timestepper isa QuasiAdamsBashforth2TimeStepper ? m.timestepper.χ : 0.1, nt, closure, nu, kap, Cnu, Ck, Cb, hasCb,
-                     m.coriolis === nothing ? 0 : 1, m.coriolis === nothing ? 0.0 : m.coriolis.f,
+                     m.coriolis isa FPlane ? 1 : 0, m.coriolis isa FPlane ? m.coriolis.f : 0.0,       # ConstantCartesianCoriolis: tilted_desc
                      buoy, idx(:b), idx(:T), idx(:S), g, α, β,
                      ntuple(i -> i <= length(fields) ? sides(fields[i]) : none, 3 + MAXTR),
                      closure == 2 ? sides(m.diffusivity_fields.νₑ) : none,
                      ntuple(i -> (closure == 2 && i <= nt) ? sides(m.diffusivity_fields.κₑ[i]) : none, MAXTR))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if bplan.column_members | bplan.field_members != 0   # background fields: ocn_background_desc { column_members, field_members }; forcing rides along
+    m.coriolis === nothing || m.coriolis isa FPlane || m.coriolis isa ConstantCartesianCoriolis || error("coriolis $(typeof(m.coriolis)) is outside the path")
+    td = tilted_desc(m)
+    if td.has_gravity_vector != 0 || td.coriolis_cartesian != 0   # a gravity unit vector or a Cartesian rotation: the general creator; forcing and background ride along
+        fd = UInt32[fplan.column_fields, fplan.field_fields]; bd = UInt32[bplan.column_members, bplan.field_members]
+        GC.@preserve keep fd bd check(ccall((:ocn_model_create_tilted, libocnhip), Cint,
+                                            (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ptr{UInt32}, Ptr{UInt32}, Ref{TiltedDesc}, Ref{Ptr{Cvoid}}),
+                                            gridh, desc, C_NULL, UInt32(m.stokes_drift === nothing ? 0 : 1), fd, bd, td, h), arch.ctx)
+    elseif bplan.column_members | bplan.field_members != 0   # background fields: ocn_background_desc { column_members, field_members }; forcing rides along
         fd = UInt32[fplan.column_fields, fplan.field_fields]; bd = UInt32[bplan.column_members, bplan.field_members]
         GC.@preserve keep fd bd check(ccall((:ocn_model_create_background, libocnhip), Cint,
                                             (Ptr{Cvoid}, Ref{ModelDesc}, Ptr{Cvoid}, UInt32, Ptr{UInt32}, Ptr{UInt32}, Ref{Ptr{Cvoid}}),
