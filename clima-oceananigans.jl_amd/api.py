@@ -594,6 +594,24 @@ def CenterField(grid):
     return Field((Center, Center, Center), grid)
 
 
+class _StageSlots:
+    """what each of the library's three stage slots holds of one feature's column tables, and how often a slot's contents changed"""
+
+    def __init__(self, ctx):
+        self.ctx, self.sent, self.uploads = ctx, [None] * 3, 0
+
+    def set(self, slot, tabs, send):
+        """``tabs``: {item: table}.  ``send(item, table)``, the library call, for every item whose table differs from what the slot holds."""
+        sent = self.sent[slot]
+        changed = [k for k in tabs if sent is None or not np.array_equal(tabs[k], sent[k])]
+        if not changed:
+            return
+        for k in changed:
+            check(send(k, tabs[k]), self.ctx.h)
+        self.sent[slot] = tabs
+        self.uploads += 1
+
+
 class NonhydrostaticModel:
     """``NonhydrostaticModel(; grid, advection, buoyancy, coriolis, closure, boundary_conditions, tracers,
     timestepper)`` (Models/NonhydrostaticModels/nonhydrostatic_model.jl:102-203)."""
@@ -607,8 +625,7 @@ class NonhydrostaticModel:
         if stokes_drift is not None and grid.topo[2] == Flat:
             raise ValueError("UniformStokesDrift on a grid with a Flat z is outside the path")
         self.stokes_drift = stokes_drift
-        self.stokes_uploads = 0            # table sets sent to the library so far (one per stage slot whose contents changed)
-        self._stokes_sent = [None] * 3     # what each stage slot holds
+        self._stokes, self._forcing, self._background = _StageSlots(self.ctx), _StageSlots(self.ctx), _StageSlots(self.ctx)
         if isinstance(tracers, str):
             tracers = (tracers,)
         self.tracer_names = tuple(tracers)
@@ -641,7 +658,7 @@ class NonhydrostaticModel:
                 d.amd_Ckappa[i] = float(closure.Ckappa[n] if isinstance(closure.Ckappa, dict) else closure.Ckappa)
         else:
             raise OcnError("OCN_EUNSUPPORTED: closure outside the path")
-        td = L.TiltedDesc()                # tilted gravity, Cartesian Coriolis, quadratic drag: ocn_model_create_tilted when any is set
+        td = L.TiltedDesc()                # tilted gravity, Cartesian Coriolis, quadratic drag
         if isinstance(coriolis, ConstantCartesianCoriolis):
             td.coriolis_cartesian, td.fx, td.fy, td.fz = 1, coriolis.fx, coriolis.fy, coriolis.fz
         elif coriolis is not None:
@@ -668,7 +685,7 @@ class NonhydrostaticModel:
                 d.T_index, d.S_index = self.tracer_names.index("T"), self.tracer_names.index("S")
                 d.g, d.alpha, d.beta = buoyancy.g, buoyancy.alpha, buoyancy.beta
         self._keep = []
-        names = ("u", "v", "w") + self.tracer_names
+        names = self._names = ("u", "v", "w") + self.tracer_names
         def fill(slot, side, bc):
             if isinstance(bc, QuadraticDragBC):
                 raise ValueError(f"QuadraticDragBC on the {side} of a diffusivity field: it is offered on the bottom and top of u and v")
@@ -716,61 +733,33 @@ class NonhydrostaticModel:
         self.h = C.c_void_p()
         # forcing: {field: one of Relaxation / Forcing / function of (x, y, z, t), or a tuple of them}
         self.forcing = self._regularize_forcing(forcing, names)
-        self.forcing_uploads = 0           # column-table sets sent so far (one per stage slot whose contents changed)
-        self._forcing_sent = [None] * 3    # what each stage slot holds
         # background_fields: {name: function of (x, y, z, t) / BackgroundField / Field}, names among u, v, w and the tracers
         self.background_fields = self._regularize_background(background_fields, names)
-        self.background_uploads = 0        # column-table sets sent so far (one per stage slot whose contents changed)
-        self._background_sent = [None] * 3
-        tilted = bool(td.has_gravity_vector or td.coriolis_cartesian or any(td.drag[f][s].present for f in range(2) for s in range(2)))
-        if self.forcing or self.background_fields or tilted:
-            fd = L.ForcingDesc()
-            for n, parts in self.forcing.items():
-                bit = 1 << names.index(n)
-                if parts["col_relax"] is not None or parts["col_F"]:
-                    fd.column_fields |= bit
-                if parts["fld_relax"] is not None or parts["fld_F"]:
-                    fd.field_fields |= bit
-            bd = L.BackgroundDesc()
-            for n, mem in self.background_fields.members().items():
-                if isinstance(mem, BackgroundField) and mem.column:
-                    bd.column_members |= 1 << names.index(n)
-                else:
-                    bd.field_members |= 1 << names.index(n)
-            sd = None
-            if smag is not None:
-                sd = L.SmagorinskyLillyDesc()
-                sd.C, sd.Cb = smag.C, smag.Cb
-                for i, n in enumerate(self.tracer_names):
-                    if isinstance(smag.Pr, dict) and n not in smag.Pr:
-                        raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
-                    sd.Pr[i] = smag.Pr_of(n)
-            features = L.FEATURE_STOKES_DRIFT if stokes_drift is not None else 0
-            if tilted:
-                check(self.lib.ocn_model_create_tilted(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
-                                                       C.byref(fd), C.byref(bd), C.byref(td), C.byref(self.h)), self.ctx.h)
-            elif self.background_fields:
-                check(self.lib.ocn_model_create_background(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
-                                                           C.byref(fd), C.byref(bd), C.byref(self.h)), self.ctx.h)
+        fd = L.ForcingDesc()
+        for n, parts in self.forcing.items():
+            bit = 1 << names.index(n)
+            if parts["col_relax"] is not None or parts["col_F"]:
+                fd.column_fields |= bit
+            if parts["fld_relax"] is not None or parts["fld_F"]:
+                fd.field_fields |= bit
+        bd = L.BackgroundDesc()
+        for n, mem in self.background_fields.members().items():
+            if isinstance(mem, BackgroundField) and mem.column:
+                bd.column_members |= 1 << names.index(n)
             else:
-                check(self.lib.ocn_model_create_forced(grid.h, C.byref(d), C.byref(sd) if sd is not None else None, features,
-                                                       C.byref(fd), C.byref(self.h)), self.ctx.h)
-        elif smag is None and stokes_drift is None:
-            check(self.lib.ocn_model_create(grid.h, C.byref(d), C.byref(self.h)), self.ctx.h)
-        elif smag is None:
-            check(self.lib.ocn_model_create_with(grid.h, C.byref(d), None, L.FEATURE_STOKES_DRIFT, C.byref(self.h)), self.ctx.h)
-        else:
+                bd.field_members |= 1 << names.index(n)
+        sd = None
+        if smag is not None:
             sd = L.SmagorinskyLillyDesc()
             sd.C, sd.Cb = smag.C, smag.Cb
             for i, n in enumerate(self.tracer_names):
                 if isinstance(smag.Pr, dict) and n not in smag.Pr:
                     raise ValueError(f"SmagorinskyLilly: Pr has no entry for tracer {n}")
                 sd.Pr[i] = smag.Pr_of(n)
-            if stokes_drift is None:
-                check(self.lib.ocn_model_create_smagorinsky_lilly(grid.h, C.byref(d), C.byref(sd), C.byref(self.h)), self.ctx.h)
-            else:
-                check(self.lib.ocn_model_create_with(grid.h, C.byref(d), C.byref(sd), L.FEATURE_STOKES_DRIFT, C.byref(self.h)),
-                      self.ctx.h)
+        # the widest creator: the library treats a null or all-zero part as absent, as its narrower creators do
+        check(self.lib.ocn_model_create_tilted(grid.h, C.byref(d), None if sd is None else C.byref(sd),
+                                               0 if stokes_drift is None else L.FEATURE_STOKES_DRIFT, C.byref(fd), C.byref(bd), C.byref(td),
+                                               C.byref(self.h)), self.ctx.h)
         H = (C.c_int32 * 3)()
         check(self.lib.ocn_model_halo(self.h, C.byref(H)), self.ctx.h)
         self.halo = tuple(H)
@@ -801,19 +790,19 @@ class NonhydrostaticModel:
         except Exception:
             pass
 
+    # table sets sent to the library so far: one per stage slot whose contents changed
+    stokes_uploads = property(lambda self: self._stokes.uploads)
+    forcing_uploads = property(lambda self: self._forcing.uploads)
+    background_uploads = property(lambda self: self._background.uploads)
+
     # ---- UniformStokesDrift: host evaluation of the drift's functions into the library's stage slots ------------------------
     def _stokes_set(self, slot, t):
         _, _, Z = self.nodes("u")
         _, _, ZF = self.nodes("w")
         Nz = self.grid.Nz
-        tab = self.stokes_drift.tables(Z.ravel()[:Nz], ZF.ravel()[:Nz], t)
-        if self._stokes_sent[slot] is not None and np.array_equal(tab, self._stokes_sent[slot]):
-            return
         PD = C.POINTER(C.c_double)
-        ptr = [tab[i].ctypes.data_as(PD) for i in range(6)]
-        check(self.lib.ocn_model_set_stokes_drift(self.h, slot, *ptr, Nz), self.ctx.h)
-        self._stokes_sent[slot] = tab
-        self.stokes_uploads += 1
+        self._stokes.set(slot, {0: self.stokes_drift.tables(Z.ravel()[:Nz], ZF.ravel()[:Nz], t)}, lambda _, tab:
+                         self.lib.ocn_model_set_stokes_drift(self.h, slot, *[tab[i].ctypes.data_as(PD) for i in range(6)], Nz))
 
     def stage_times(self, dt):
         """clock times at which the stages of ``time_step(model, dt)`` compute their tendencies (the library's own sums)"""
@@ -917,30 +906,18 @@ class NonhydrostaticModel:
     def set_forcing_field(self, name, sigma=None, tau=None, F=None):
         """replace the field-form arrays of ``name`` ((Nx, Ny, Nz) each; ``None``: absent).  Synchronises the model's stream."""
         g = self.grid
-        names = ("u", "v", "w") + self.tracer_names
         PD = C.POINTER(C.c_double)
         keep = [None if a is None else np.asfortranarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (g.Nx, g.Ny, g.Nz)))
                 for a in (sigma, tau, F)]
         ptr = [None if a is None else a.ctypes.data_as(PD) for a in keep]
-        check(self.lib.ocn_model_set_forcing_field(self.h, names.index(name), *ptr, g.Nx, g.Ny, g.Nz), self.ctx.h)
+        check(self.lib.ocn_model_set_forcing_field(self.h, self._names.index(name), *ptr, g.Nx, g.Ny, g.Nz), self.ctx.h)
 
     def _forcing_set(self, slot, t):
-        names = ("u", "v", "w") + self.tracer_names
-        cols = [n for n, p in self.forcing.items() if p["col_relax"] is not None or p["col_F"]]
-        if not cols:
-            return
-        tabs = {n: self._forcing_column_tables(n, t) for n in cols}
-        sent = self._forcing_sent[slot]
-        changed = [n for n in cols if sent is None or not np.array_equal(tabs[n], sent[n])]
-        if not changed:
-            return
         PD = C.POINTER(C.c_double)
-        for n in changed:
-            tab = np.ascontiguousarray(tabs[n])
-            check(self.lib.ocn_model_set_forcing_column(self.h, names.index(n), slot, *[tab[i].ctypes.data_as(PD) for i in range(3)],
-                                                        self.grid.Nz), self.ctx.h)
-        self._forcing_sent[slot] = tabs
-        self.forcing_uploads += 1
+        cols = [n for n, p in self.forcing.items() if p["col_relax"] is not None or p["col_F"]]
+        self._forcing.set(slot, {n: np.ascontiguousarray(self._forcing_column_tables(n, t)) for n in cols}, lambda n, tab:
+                          self.lib.ocn_model_set_forcing_column(self.h, self._names.index(n), slot,
+                                                                *[tab[i].ctypes.data_as(PD) for i in range(3)], self.grid.Nz))
 
     def refresh_forcing(self):
         """for the kernel-by-kernel verbs (``ocn_compute_tendencies`` ...): evaluate the column-form forcing at ``model.time`` into
@@ -1033,30 +1010,19 @@ class NonhydrostaticModel:
     def set_background_field(self, name, array):
         """replace the field-form array of member ``name``: the parent array of the field it belongs to, halo entries included.
         Synchronises the model's stream."""
-        names = ("u", "v", "w") + self.tracer_names
         total = (getattr(self, name) if name in "uvw" else self.tracers[name]).total
         a = np.asarray(array, dtype=np.float64)
         if a.shape != total:
             raise ValueError(f"background field {name}: an array of shape {a.shape} for a parent array of shape {total} "
                              "(a Field must live on a grid with the model's halo)")
         a = np.asfortranarray(a)
-        check(self.lib.ocn_model_set_background_field(self.h, names.index(name), a.ctypes.data_as(C.POINTER(C.c_double)), *total), self.ctx.h)
+        check(self.lib.ocn_model_set_background_field(self.h, self._names.index(name), a.ctypes.data_as(C.POINTER(C.c_double)), *total), self.ctx.h)
 
     def _background_set(self, slot, t):
-        names = ("u", "v", "w") + self.tracer_names
         cols = [n for n, mem in self.background_fields.members().items() if isinstance(mem, BackgroundField) and mem.column]
-        if not cols:
-            return
-        tabs = {n: np.ascontiguousarray(self._background_column_table(n, t)) for n in cols}
-        sent = self._background_sent[slot]
-        changed = [n for n in cols if sent is None or not np.array_equal(tabs[n], sent[n])]
-        if not changed:
-            return
-        for n in changed:
-            check(self.lib.ocn_model_set_background_column(self.h, names.index(n), slot, tabs[n].ctypes.data_as(C.POINTER(C.c_double)),
-                                                           tabs[n].size), self.ctx.h)
-        self._background_sent[slot] = tabs
-        self.background_uploads += 1
+        self._background.set(slot, {n: np.ascontiguousarray(self._background_column_table(n, t)) for n in cols}, lambda n, tab:
+                             self.lib.ocn_model_set_background_column(self.h, self._names.index(n), slot,
+                                                                      tab.ctypes.data_as(C.POINTER(C.c_double)), tab.size))
 
     def refresh_background(self):
         """for the kernel-by-kernel verbs (``ocn_compute_tendencies`` ...): evaluate the column-form members at ``model.time`` into
@@ -1142,15 +1108,12 @@ class NonhydrostaticModel:
 
 def time_step(model, dt, euler=False):
     """``time_step!(model, Δt; euler=false)``."""
-    if getattr(model, "stokes_drift", None) is not None:
-        for slot, t in enumerate(model.stage_times(dt)):   # outside any graph capture; only slots whose tables changed are sent
-            model._stokes_set(slot, t)
-    if getattr(model, "forcing", None):
-        for slot, t in enumerate(model.stage_times(dt)):
-            model._forcing_set(slot, t)
-    if getattr(model, "background_fields", None):
-        for slot, t in enumerate(model.stage_times(dt)):
-            model._background_set(slot, t)
+    setters = [getattr(model, s) for a, s in (("stokes_drift", "_stokes_set"), ("forcing", "_forcing_set"), ("background_fields", "_background_set"))
+               if getattr(model, a, None)]
+    times = model.stage_times(dt) if setters else ()   # outside any graph capture; only slots whose tables changed are sent
+    for set_slot in setters:
+        for slot, t in enumerate(times):
+            set_slot(slot, t)
     check(model.lib.ocn_time_step(model.h, float(dt), int(bool(euler))), model.ctx.h)
 
 

@@ -879,354 +879,66 @@ static int step_graphed(ocn_model* m, double dt, int force_euler) {
 }
 #endif
 
-// ocn_model_create, ocn_model_create_smagorinsky_lilly (smag != null), ocn_model_create_with, ocn_model_create_forced,
-// ocn_model_create_background and ocn_model_create_tilted share this body
-static int model_create(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, bool stokes,
-                        const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
-                        ocn_model** out) {
-  ocn_ctx* ctx = g->ctx;
-  if (tilted) {
-    if (g->dist || g->dist_y || ctx->nranks > 1) {
-      ocn_set_error(ctx, "tilted gravity, Cartesian Coriolis and quadratic drag on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) are not supported");
-      return OCN_EUNSUPPORTED;
-    }
-    if (tilted->has_gravity_vector && desc->buoyancy == OCN_BUOYANCY_NONE) {
-      ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs a buoyancy model (desc->buoyancy is OCN_BUOYANCY_NONE)");
-      return OCN_EINVAL;
-    }
-    if (tilted->has_gravity_vector && desc->n_tracers >= 0 && desc->n_tracers <= OCN_MAX_TRACERS) {
-      auto ok = [&](int i) { return i >= 0 && i < desc->n_tracers; };
-      if ((desc->buoyancy == OCN_BUOYANCY_TRACER && !ok(desc->b_index)) ||
-          (desc->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(desc->T_index) && ok(desc->S_index)))) {
-        ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs the buoyancy model's tracers");
-        return OCN_EINVAL;
-      }
-    }
-    if (tilted->coriolis_cartesian && desc->coriolis_fplane) {
-      ocn_set_error(ctx, "ocn_model_create_tilted: Cartesian Coriolis together with desc->coriolis_fplane (a model has one rotation)");
-      return OCN_EINVAL;
-    }
-    for (int f = 0; f < 2; ++f)
-      for (int sd = 0; sd < 2; ++sd) {
-        if (!tilted->drag[f][sd].present) continue;
-        if (g->topo[2] != OCN_BOUNDED) {
-          ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, but z is not Bounded", sd ? "top" : "bottom", f ? "v" : "u");
-          return OCN_EINVAL;
-        }
-        if (desc->bcs[f][OCN_BOTTOM + sd].kind != OCN_BC_DEFAULT) {
-          ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, which already has a boundary condition", sd ? "top" : "bottom",
-                        f ? "v" : "u");
-          return OCN_EINVAL;
-        }
-      }
+// ---- staged column tables (internal.h StagedTables) --------------------------------------------------------------------
+bool StagedTables::alloc(int items, size_t length) {
+  nitem = items;
+  len = length;
+  const size_t nb = (size_t)3 * nitem * len * sizeof(double);
+  stage = (double*)calloc(1, nb);
+  return stage && hipMalloc((void**)&dev, nb) == hipSuccess && hipMemset(dev, 0, nb) == hipSuccess;
+}
+
+int StagedTables::upload(ocn_ctx* ctx, int s, int item, const double* const* runs, int nruns, size_t runlen) {
+  double* st = stage + (slot(s, item) - dev);
+  hipEvent_t& e = ev[s][item];
+  if (e) OCN_HIP_CHECK(ctx, hipEventSynchronize(e));
+  else OCN_HIP_CHECK(ctx, hipEventCreate(&e));
+  for (int r = 0; r < nruns; ++r) {
+    if (runs[r]) memcpy(st + r * runlen, runs[r], runlen * sizeof(double));
+    else memset(st + r * runlen, 0, runlen * sizeof(double));
   }
-  const uint32_t bcol = background ? background->column_members : 0u, bfld = background ? background->field_members : 0u;
-  if ((bcol | bfld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((bcol | bfld) >> (3 + desc->n_tracers)) != 0)) {
-    ocn_set_error(ctx, "ocn_model_create_background: member masks 0x%x / 0x%x name members beyond u, v, w and the model's %d tracers", bcol, bfld,
-                  desc->n_tracers);
-    return OCN_EINVAL;
-  }
-  if (bcol & bfld) {
-    ocn_set_error(ctx, "ocn_model_create_background: members 0x%x are declared in both forms (a member has one)", bcol & bfld);
-    return OCN_EINVAL;
-  }
-  if ((bcol | bfld) && (g->dist || g->dist_y || ctx->nranks > 1)) {
-    ocn_set_error(ctx, "background fields on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) are not supported");
-    return OCN_EUNSUPPORTED;
-  }
-  const uint32_t fcol = forcing ? forcing->column_fields : 0u, ffld = forcing ? forcing->field_fields : 0u;
-  if ((fcol | ffld) && (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS || ((fcol | ffld) >> (3 + desc->n_tracers)) != 0)) {
-    ocn_set_error(ctx, "ocn_model_create_forced: forcing masks 0x%x / 0x%x name fields beyond u, v, w and the model's %d tracers", fcol, ffld,
-                  desc->n_tracers);
-    return OCN_EINVAL;
-  }
-  if ((fcol | ffld) && (g->dist || g->dist_y || ctx->nranks > 1)) {
-    ocn_set_error(ctx, "forcing on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) is not supported");
-    return OCN_EUNSUPPORTED;
-  }
-  if (stokes && g->topo[2] == OCN_FLAT) {
-    ocn_set_error(ctx, "UniformStokesDrift on a grid with a Flat z is outside the path (its terms are vertical averages)");
-    return OCN_EUNSUPPORTED;
-  }
-  if (stokes && (g->dist || g->dist_y || ctx->nranks > 1)) {
-    ocn_set_error(ctx, "UniformStokesDrift on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) is not supported");
-    return OCN_EUNSUPPORTED;
-  }
-  if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
-  if (desc->advection < OCN_ADV_NONE || desc->advection > OCN_ADV_U3) return OCN_EINVAL;
-  if (desc->closure == OCN_CLOSURE_AMD && (g->topo[0] == OCN_FLAT || g->topo[1] == OCN_FLAT || g->topo[2] == OCN_FLAT)) {
-    ocn_set_error(ctx, "AnisotropicMinimumDissipation on a grid with a Flat direction is outside the path");
-    return OCN_EUNSUPPORTED;
-  }
-  if (desc->closure == OCN_CLOSURE_AMD && desc->amd_has_Cb) {
-    auto ok = [&](int i) { return i >= 0 && i < desc->n_tracers; };
-    if ((desc->buoyancy == OCN_BUOYANCY_TRACER && !ok(desc->b_index)) ||
-        (desc->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(desc->T_index) && ok(desc->S_index)))) {
-      ocn_set_error(ctx, "AMD buoyancy modification needs the buoyancy model's tracers");
-      return OCN_EINVAL;
-    }
-  }
-  // halo inflation (nonhydrostatic_model.jl:140-148; Advection.jl:40)
-  static const int buffer[8] = {0, 0, 1, 2, 2, 2, 1, 1};   // boundary_buffer of NONE, C2, C4, U5, WENO5 (Z, JS), U1, U3
-  // The reference builds a NEW grid with the wider halo (with_halo); so does this: the caller's grid, and any
-  // model already living on it, keep their halos, spacing tables and layouts.
-  int need = buffer[desc->advection] + 1;
-  bool changed = false;
-  for (int d = 0; d < 3; ++d)
-    if (g->topo[d] != OCN_FLAT && g->H[d] < need) changed = true;
-  ocn_grid* own = nullptr;
-  if (changed) {
-    own = new ocn_grid(*g);
-    own->d_dzc = own->d_dzf = own->d_rdzc = own->d_rdzf = nullptr;   // grid_build_dev allocates the copy's own tables
-    for (int d = 0; d < 3; ++d)
-      if (own->topo[d] != OCN_FLAT && own->H[d] < need) own->H[d] = need;
-    int rc = grid_build_dev(own);
-    if (rc) {
-      ocn_grid_destroy(own);
-      return rc;
-    }
-    g = own;
-  }
-  ocn_model* m = new ocn_model;
-  m->own_grid = own;
-  m->g = g;
-  m->ctx = ctx;
-  m->d = *desc;
-  m->nt = desc->n_tracers;
-  if (smag) {
-    // the molecular part of a (SmagorinskyLilly, ScalarDiffusivity) tuple stays in d.nu / d.kappa; alone: none
-    if (desc->closure == OCN_CLOSURE_NONE) {
-      m->d.nu = 0.0;
-      for (int t = 0; t < OCN_MAX_TRACERS; ++t) m->d.kappa[t] = 0.0;
-    }
-    m->d.closure = OCN_CLOSURE_SMAG;
-    m->smag_C = smag->C;
-    m->smag_Cb = smag->Cb;
-    for (int t = 0; t < m->nt; ++t) m->smag_rPr[t] = 1.0 / smag->Pr[t];
-  }
-  if (tilted) {
-    m->tl = *tilted;
-    m->tilt_terms = tilted->has_gravity_vector || tilted->coriolis_cartesian;
-    for (int f = 0; f < 2; ++f)
-      for (int sd = 0; sd < 2; ++sd) m->drag_any = m->drag_any || tilted->drag[f][sd].present;
-  }
-  m->gd = g->dev;
-  m->gd.nb = buffer[desc->advection];
-  int rc = 0;
-  rc |= field_alloc(m, m->u, OCN_FACE, OCN_CENTER, OCN_CENTER);
-  rc |= field_alloc(m, m->v, OCN_CENTER, OCN_FACE, OCN_CENTER);
-  rc |= field_alloc(m, m->w, OCN_CENTER, OCN_CENTER, OCN_FACE);
-  rc |= field_alloc(m, m->pNHS, OCN_CENTER, OCN_CENTER, OCN_CENTER);
-  if (g->topo[2] != OCN_FLAT) rc |= field_alloc(m, m->pHY, OCN_CENTER, OCN_CENTER, OCN_CENTER);
-  for (int t = 0; t < m->nt; ++t) rc |= field_alloc(m, m->tr[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
-  if (desc->closure == OCN_CLOSURE_AMD) {
-    // DiffusivityFields(grid, tracers, bcs, ::AMD): nu_e and kappa_e per tracer, CenterFields with default BCs
-    rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
-    for (int t = 0; t < m->nt; ++t) rc |= field_alloc(m, m->kappa_e[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
-  }
-  // DiffusivityFields(grid, tracers, bcs, ::SmagorinskyLilly) (smagorinsky_lilly.jl:209-222): nu_e alone; kappa_e is nu_e / Pr, an operation
-  if (smag) rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
-  for (int f = 0; f < 3 + m->nt; ++f) {
-    int lx = f == 0, ly = f == 1, lz = f == 2;
-    rc |= field_alloc(m, m->Gn[f], lx, ly, lz);
-    rc |= field_alloc(m, m->Gm[f], lx, ly, lz);
-  }
-  if (rc) {
-    ocn_model_destroy(m);
-    return OCN_ENOMEM;
-  }
-  default_bcs(m, m->u, false);
-  default_bcs(m, m->v, false);
-  default_bcs(m, m->w, false);
-  default_bcs(m, m->pNHS, true);
-  if (m->pHY.present) default_bcs(m, m->pHY, true);
-  for (int t = 0; t < m->nt; ++t) default_bcs(m, m->tr[t], false);
-  if (m->nu_e.present) {
-    default_bcs(m, m->nu_e, true);
-    for (int t = 0; t < m->nt; ++t)
-      if (m->kappa_e[t].present) default_bcs(m, m->kappa_e[t], true);
-  }
-  // user boundary conditions
-  // u, v, w, tracers, then -- AnisotropicMinimumDissipation only -- the diffusivity fields nu_e and kappa_e of every tracer
-  // (boundary_conditions = (; kappa_e = (; b = ...)) of the reference: nonhydrostatic_model.jl:150-160, test_boundary_conditions_integration.jl:52-66)
-  const int nbc = 3 + m->nt + (smag ? 1 : desc->closure == OCN_CLOSURE_AMD ? 1 + m->nt : 0);
-  for (int f = 0; f < nbc; ++f) {
-    const int fd = f - (3 + m->nt);   // index among the diffusivity fields
-    Field* fld = f == 0 ? &m->u : f == 1 ? &m->v : f == 2 ? &m->w : f < 3 + m->nt ? &m->tr[f - 3] : fd == 0 ? &m->nu_e : &m->kappa_e[fd - 1];
-    for (int s = 0; s < 6; ++s) {
-      const ocn_bc& b = f < 3 + m->nt ? desc->bcs[f][s] : fd == 0 ? desc->nu_bcs[s] : desc->kappa_bcs[fd - 1][s];
-      if (b.kind == OCN_BC_DEFAULT) continue;
-      int dim = s / 2;
-      if (g->topo[dim] != OCN_BOUNDED) {
-        if (b.kind == OCN_BC_PERIODIC || b.kind == OCN_BC_NONE) continue;
-        ocn_set_error(ctx, "non-periodic boundary condition on a non-Bounded side (field %d side %d)", f, s);
-        ocn_model_destroy(m);
-        return OCN_EINVAL;
-      }
-      BCdev bd{b.kind, b.value, nullptr};
-      if (b.array) {
-        // arrays span the two other directions' interior sizes (boundary_condition.jl getbc for arrays)
-        size_t nn = dim == 0 ? (size_t)g->N[1] * g->N[2] : dim == 1 ? (size_t)g->N[0] * g->N[2] : (size_t)g->N[0] * g->N[1];
-        double* dptr = nullptr;
-        if (hipMalloc((void**)&dptr, nn * sizeof(double)) != hipSuccess) {
-          ocn_model_destroy(m);
-          return OCN_ENOMEM;
-        }
-        hipMemcpy(dptr, b.array, nn * sizeof(double), hipMemcpyHostToDevice);
-        m->owned.push_back(dptr);
-        bd.arr = dptr;
-      }
-      fld->bc[s] = bd;
-    }
-  }
-  // a quadratic drag is the Flux condition of its side: the halo fill treats it as one, k_drag_flux adds the flux to G^n
-  for (int f = 0; f < 2; ++f)
-    for (int sd = 0; sd < 2; ++sd)
-      if (m->tl.drag[f][sd].present) (f == 0 ? m->u : m->v).bc[OCN_BOTTOM + sd] = BCdev{OCN_BC_FLUX, 0.0, nullptr};
-  if (g->dist && hipMalloc((void**)&m->phi_below, (size_t)g->N[0] * g->N[1] * sizeof(double)) != hipSuccess) {
-    ocn_model_destroy(m);
-    return OCN_ENOMEM;
-  }
-  if (desc->closure == OCN_CLOSURE_AMD && amd_build_table(m) != OCN_OK) {
-    ocn_model_destroy(m);
-    return OCN_ENOMEM;
-  }
-  if (smag) {
-    const int rs = smag_build_table(m);
-    if (rs != OCN_OK) {
-      ocn_model_destroy(m);
-      return rs;
-    }
-  }
-  if (hipMalloc((void**)&m->d_red, 64) != hipSuccess) {
-    ocn_model_destroy(m);
-    return OCN_ENOMEM;
-  }
-  if (stokes) {
-    const size_t nb = (size_t)3 * 6 * g->N[2] * sizeof(double);
-    m->stokes = 1;
-    m->stokes_stage = (double*)calloc(1, nb);
-    if (!m->stokes_stage || hipMalloc((void**)&m->stokes_dev, nb) != hipSuccess || hipMemset(m->stokes_dev, 0, nb) != hipSuccess) {
-      ocn_model_destroy(m);
-      return OCN_ENOMEM;
-    }
-  }
-  for (int f = 0; f < OCN_NF; ++f) m->force_ci[f] = -1;
-  if (fcol | ffld) {
-    m->force_col = fcol;
-    m->force_fld = ffld;
-    for (int f = 0; f < 3 + m->nt; ++f)   // u, v, w come as a block (internal.h force_col3): an undeclared one's tables stay zero
-      if ((fcol >> f & 1u) || (f < 3 && (fcol & 7u))) m->force_ci[f] = m->force_ncol++;
-    if (m->force_ncol) {
-      const size_t nb = (size_t)3 * m->force_ncol * 3 * g->N[2] * sizeof(double);
-      m->force_stage = (double*)calloc(1, nb);
-      if (!m->force_stage || hipMalloc((void**)&m->force_dev, nb) != hipSuccess || hipMemset(m->force_dev, 0, nb) != hipSuccess) {
-        ocn_model_destroy(m);
-        return OCN_ENOMEM;
-      }
-    }
-  }
-  for (int f = 0; f < OCN_NF; ++f) m->bg_ci[f] = -1;
-  if (bcol | bfld) {
-    m->bg_col = bcol;
-    m->bg_fld = bfld;
-    m->bg_len = m->w.T[2] > m->u.T[2] ? m->w.T[2] : m->u.T[2];   // every parent level of the tallest field (w with a Bounded z)
-    for (int f = 0; f < 3 + m->nt; ++f)
-      if (bcol >> f & 1u) m->bg_ci[f] = m->bg_ncol++;
-    if (m->bg_ncol) {
-      const size_t nb = (size_t)3 * m->bg_ncol * m->bg_len * sizeof(double);
-      m->bg_stage = (double*)calloc(1, nb);
-      if (!m->bg_stage || hipMalloc((void**)&m->bg_dev, nb) != hipSuccess || hipMemset(m->bg_dev, 0, nb) != hipSuccess) {
-        ocn_model_destroy(m);
-        return OCN_ENOMEM;
-      }
-    }
-    for (int f = 0; f < 3 + m->nt; ++f) {   // field form: allocated here, zero until set, so the addresses in a step graph hold
-      if (!(bfld >> f & 1u)) continue;
-      const size_t nb = bg_field_of(m, f).n * sizeof(double);
-      if (hipMalloc((void**)&m->bg_arr[f], nb) != hipSuccess || hipMemset(m->bg_arr[f], 0, nb) != hipSuccess) {
-        ocn_model_destroy(m);
-        return OCN_ENOMEM;
-      }
-    }
-  }
-  fused_read_knobs(m);
-  m->fast_path = fused_available(m) ? 1 : 0;
-  m->bz_fast = (!m->fast_path && fused_bz_available(m)) ? 1 : 0;
-  if (getenv("OCNHIP_DEBUG")) {
-    char why[256];
-    fused_describe(m, why, sizeof(why));
-    fprintf(stderr, "[ocnhip] model: %s\n", why);
-  }
-  if (m->fast_path || m->bz_fast) {
-    int r2 = field_alloc(m, m->us, OCN_FACE, OCN_CENTER, OCN_CENTER) | field_alloc(m, m->vs, OCN_CENTER, OCN_FACE, OCN_CENTER) |
-             field_alloc(m, m->ws, OCN_CENTER, OCN_CENTER, OCN_FACE);
-    for (int t = 0; t < m->nt; ++t) r2 |= field_alloc(m, m->trs[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
-    if (r2) {
-      ocn_model_destroy(m);
-      return OCN_ENOMEM;
-    }
-    for (int s = 0; s < 6; ++s) {   // the predictor is filled with the velocities' boundary conditions
-      m->us.bc[s] = m->u.bc[s];
-      m->vs.bc[s] = m->v.bc[s];
-      m->ws.bc[s] = m->w.bc[s];
-    }
-  }
-  m->solver = poisson_create(m);
-  if (!m->solver) {
-    ocn_model_destroy(m);
-    return OCN_EHIP;
-  }
-  update_state(m);  // nonhydrostatic_model.jl:200
-  ctx->models.push_back(m);
-  *out = m;
+  OCN_HIP_CHECK(ctx, hipMemcpyAsync(slot(s, item), st, nruns * runlen * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  OCN_HIP_CHECK(ctx, hipEventRecord(e, ctx->stream));
   return OCN_OK;
 }
 
-extern "C" {
-
-int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) {
-  if (!g || !desc || !out) return OCN_EINVAL;
-  if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-  return model_create(g, desc, nullptr, false, nullptr, nullptr, nullptr, out);
+void StagedTables::release() {
+  hipFree(dev);
+  free(stage);
+  for (auto& row : ev)
+    for (hipEvent_t e : row)
+      if (e) hipEventDestroy(e);
 }
 
-int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
-  return smag ? ocn_model_create_with(g, desc, smag, 0, out) : OCN_EINVAL;
+// ---- model creation ----------------------------------------------------------------------------------------------------
+// What the six creators of ocnhip.h hand to the one body below; every part may be absent (null, zero masks, no feature bit).
+struct CreateArgs {
+  const ocn_smagorinsky_lilly_desc* smag;
+  uint32_t features;
+  const ocn_forcing_desc* forcing;
+  const ocn_background_desc* background;
+  const ocn_tilted_desc* tilted;
+};
+// destroys the half-built model on every early return of model_create
+struct ModelGuard {
+  ocn_model* m;
+  ~ModelGuard() { ocn_model_destroy(m); }
+};
+static const int boundary_buffer[8] = {0, 0, 1, 2, 2, 2, 1, 1};   // of NONE, C2, C4, U5, WENO5 (Z, JS), U1, U3 (Advection.jl:40)
+
+static bool buoyancy_tracers_exist(const ocn_model_desc* d) {
+  auto ok = [&](int i) { return i >= 0 && i < d->n_tracers; };
+  return !(d->buoyancy == OCN_BUOYANCY_TRACER && !ok(d->b_index)) &&
+         !(d->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(d->T_index) && ok(d->S_index)));
 }
 
-int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features, ocn_model** out) {
-  return ocn_model_create_forced(g, desc, smag, features, nullptr, out);
+static int refuse_distributed(const ocn_grid* g, const char* what, const char* verb) {
+  if (!(g->dist || g->dist_y || g->ctx->nranks > 1)) return OCN_OK;
+  ocn_set_error(g->ctx, "%s on a distributed grid (z- or y-slabs, more than one rank, OCNHIP_FORCE_DIST) %s not supported", what, verb);
+  return OCN_EUNSUPPORTED;
 }
 
-int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
-                            const ocn_forcing_desc* forcing, ocn_model** out) {
-  return ocn_model_create_background(g, desc, smag, features, forcing, nullptr, out);
-}
-
-int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
-                                const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
-  return ocn_model_create_tilted(g, desc, smag, features, forcing, background, nullptr, out);
-}
-
-int ocn_model_create_tilted(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
-                            const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
-                            ocn_model** out) {
-  if (!g || !desc || !out) return OCN_EINVAL;
-  if (tilted && !tilted->has_gravity_vector && !tilted->coriolis_cartesian && !tilted->drag[0][0].present && !tilted->drag[0][1].present &&
-      !tilted->drag[1][0].present && !tilted->drag[1][1].present)
-    tilted = nullptr;
-  if (forcing && !(forcing->column_fields | forcing->field_fields)) forcing = nullptr;
-  if (background && !(background->column_members | background->field_members)) background = nullptr;
-  if (features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
-    ocn_set_error(g->ctx, "ocn_model_create_with: unknown feature bits 0x%x", features);
-    return OCN_EINVAL;
-  }
-  const bool stokes = (features & OCN_FEATURE_STOKES_DRIFT) != 0;
-  if (!smag) {
-    if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) return OCN_EINVAL;
-    return model_create(g, desc, nullptr, stokes, forcing, background, tilted, out);
-  }
+static int validate_smagorinsky_lilly(const ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag) {
   ocn_ctx* ctx = g->ctx;
   if (desc->n_tracers < 0 || desc->n_tracers > OCN_MAX_TRACERS) return OCN_EINVAL;
   if (desc->closure != OCN_CLOSURE_NONE && desc->closure != OCN_CLOSURE_SCALAR) {
@@ -1252,13 +964,358 @@ int ocn_model_create_tilted(ocn_grid* g, const ocn_model_desc* desc, const ocn_s
         return OCN_EINVAL;
       }
   }
-  auto ok = [&](int i) { return i >= 0 && i < desc->n_tracers; };
-  if ((desc->buoyancy == OCN_BUOYANCY_TRACER && !ok(desc->b_index)) ||
-      (desc->buoyancy == OCN_BUOYANCY_LINEAR_TS && !(ok(desc->T_index) && ok(desc->S_index)))) {
+  if (!buoyancy_tracers_exist(desc)) {
     ocn_set_error(ctx, "SmagorinskyLilly: the stability function needs the buoyancy model's tracers");
     return OCN_EINVAL;
   }
-  return model_create(g, desc, smag, stokes, forcing, background, tilted, out);
+  return OCN_OK;
+}
+
+static int validate_tilted(const ocn_grid* g, const ocn_model_desc* desc, const ocn_tilted_desc* tilted) {
+  ocn_ctx* ctx = g->ctx;
+  if (int rc = refuse_distributed(g, "tilted gravity, Cartesian Coriolis and quadratic drag", "are")) return rc;
+  if (tilted->has_gravity_vector && desc->buoyancy == OCN_BUOYANCY_NONE) {
+    ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs a buoyancy model (desc->buoyancy is OCN_BUOYANCY_NONE)");
+    return OCN_EINVAL;
+  }
+  if (tilted->has_gravity_vector && desc->n_tracers >= 0 && desc->n_tracers <= OCN_MAX_TRACERS && !buoyancy_tracers_exist(desc)) {
+    ocn_set_error(ctx, "ocn_model_create_tilted: a gravity unit vector needs the buoyancy model's tracers");
+    return OCN_EINVAL;
+  }
+  if (tilted->coriolis_cartesian && desc->coriolis_fplane) {
+    ocn_set_error(ctx, "ocn_model_create_tilted: Cartesian Coriolis together with desc->coriolis_fplane (a model has one rotation)");
+    return OCN_EINVAL;
+  }
+  for (int f = 0; f < 2; ++f)
+    for (int sd = 0; sd < 2; ++sd) {
+      if (!tilted->drag[f][sd].present) continue;
+      if (g->topo[2] != OCN_BOUNDED) {
+        ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, but z is not Bounded", sd ? "top" : "bottom", f ? "v" : "u");
+        return OCN_EINVAL;
+      }
+      if (desc->bcs[f][OCN_BOTTOM + sd].kind != OCN_BC_DEFAULT) {
+        ocn_set_error(ctx, "ocn_model_create_tilted: quadratic drag on the %s of %s, which already has a boundary condition", sd ? "top" : "bottom",
+                      f ? "v" : "u");
+        return OCN_EINVAL;
+      }
+    }
+  return OCN_OK;
+}
+
+// every refusal that needs no allocation, in the order the callers know
+static int create_validate(const ocn_grid* g, const ocn_model_desc* desc, const CreateArgs& a) {
+  ocn_ctx* ctx = g->ctx;
+  if (a.features & ~(uint32_t)OCN_FEATURE_STOKES_DRIFT) {
+    ocn_set_error(ctx, "ocn_model_create_with: unknown feature bits 0x%x", a.features);
+    return OCN_EINVAL;
+  }
+  if (a.smag) {
+    if (int rc = validate_smagorinsky_lilly(g, desc, a.smag)) return rc;
+  } else if (desc->closure < OCN_CLOSURE_NONE || desc->closure > OCN_CLOSURE_AMD) {
+    return OCN_EINVAL;
+  }
+  if (a.tilted)
+    if (int rc = validate_tilted(g, desc, a.tilted)) return rc;
+  const bool tracers_ok = desc->n_tracers >= 0 && desc->n_tracers <= OCN_MAX_TRACERS;
+  const uint32_t bcol = a.background ? a.background->column_members : 0u, bfld = a.background ? a.background->field_members : 0u;
+  if ((bcol | bfld) && (!tracers_ok || ((bcol | bfld) >> (3 + desc->n_tracers)) != 0)) {
+    ocn_set_error(ctx, "ocn_model_create_background: member masks 0x%x / 0x%x name members beyond u, v, w and the model's %d tracers", bcol, bfld,
+                  desc->n_tracers);
+    return OCN_EINVAL;
+  }
+  if (bcol & bfld) {
+    ocn_set_error(ctx, "ocn_model_create_background: members 0x%x are declared in both forms (a member has one)", bcol & bfld);
+    return OCN_EINVAL;
+  }
+  if (bcol | bfld)
+    if (int rc = refuse_distributed(g, "background fields", "are")) return rc;
+  const uint32_t fcol = a.forcing ? a.forcing->column_fields : 0u, ffld = a.forcing ? a.forcing->field_fields : 0u;
+  if ((fcol | ffld) && (!tracers_ok || ((fcol | ffld) >> (3 + desc->n_tracers)) != 0)) {
+    ocn_set_error(ctx, "ocn_model_create_forced: forcing masks 0x%x / 0x%x name fields beyond u, v, w and the model's %d tracers", fcol, ffld,
+                  desc->n_tracers);
+    return OCN_EINVAL;
+  }
+  if (fcol | ffld)
+    if (int rc = refuse_distributed(g, "forcing", "is")) return rc;
+  if (a.features & OCN_FEATURE_STOKES_DRIFT) {
+    if (g->topo[2] == OCN_FLAT) {
+      ocn_set_error(ctx, "UniformStokesDrift on a grid with a Flat z is outside the path (its terms are vertical averages)");
+      return OCN_EUNSUPPORTED;
+    }
+    if (int rc = refuse_distributed(g, "UniformStokesDrift", "is")) return rc;
+  }
+  if (!tracers_ok) return OCN_EINVAL;
+  if (desc->advection < OCN_ADV_NONE || desc->advection > OCN_ADV_U3) return OCN_EINVAL;
+  if (desc->closure == OCN_CLOSURE_AMD && (g->topo[0] == OCN_FLAT || g->topo[1] == OCN_FLAT || g->topo[2] == OCN_FLAT)) {
+    ocn_set_error(ctx, "AnisotropicMinimumDissipation on a grid with a Flat direction is outside the path");
+    return OCN_EUNSUPPORTED;
+  }
+  if (desc->closure == OCN_CLOSURE_AMD && desc->amd_has_Cb && !buoyancy_tracers_exist(desc)) {
+    ocn_set_error(ctx, "AMD buoyancy modification needs the buoyancy model's tracers");
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+
+// halo inflation (nonhydrostatic_model.jl:140-148).  The reference builds a NEW grid with the wider halo (with_halo); so does
+// this: the caller's grid, and any model already living on it, keep their halos, spacing tables and layouts.
+static int create_inflate_halo(ocn_model* m, ocn_grid* g) {
+  const int need = boundary_buffer[m->d.advection] + 1;
+  bool changed = false;
+  for (int d = 0; d < 3; ++d)
+    if (g->topo[d] != OCN_FLAT && g->H[d] < need) changed = true;
+  m->g = g;
+  if (!changed) return OCN_OK;
+  ocn_grid* own = m->g = m->own_grid = new ocn_grid(*g);
+  own->d_dzc = own->d_dzf = own->d_rdzc = own->d_rdzf = nullptr;   // grid_build_dev allocates the copy's own tables
+  for (int d = 0; d < 3; ++d)
+    if (own->topo[d] != OCN_FLAT && own->H[d] < need) own->H[d] = need;
+  return grid_build_dev(own);
+}
+
+// the model's fields with their default boundary conditions
+static int create_fields(ocn_model* m, bool smag) {
+  int rc = 0;
+  rc |= field_alloc(m, m->u, OCN_FACE, OCN_CENTER, OCN_CENTER);
+  rc |= field_alloc(m, m->v, OCN_CENTER, OCN_FACE, OCN_CENTER);
+  rc |= field_alloc(m, m->w, OCN_CENTER, OCN_CENTER, OCN_FACE);
+  rc |= field_alloc(m, m->pNHS, OCN_CENTER, OCN_CENTER, OCN_CENTER);
+  if (m->g->topo[2] != OCN_FLAT) rc |= field_alloc(m, m->pHY, OCN_CENTER, OCN_CENTER, OCN_CENTER);
+  for (int t = 0; t < m->nt; ++t) rc |= field_alloc(m, m->tr[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
+  if (m->d.closure == OCN_CLOSURE_AMD) {
+    // DiffusivityFields(grid, tracers, bcs, ::AMD): nu_e and kappa_e per tracer, CenterFields with default BCs
+    rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
+    for (int t = 0; t < m->nt; ++t) rc |= field_alloc(m, m->kappa_e[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
+  }
+  // DiffusivityFields(grid, tracers, bcs, ::SmagorinskyLilly) (smagorinsky_lilly.jl:209-222): nu_e alone; kappa_e is nu_e / Pr, an operation
+  if (smag) rc |= field_alloc(m, m->nu_e, OCN_CENTER, OCN_CENTER, OCN_CENTER);
+  for (int f = 0; f < 3 + m->nt; ++f) {
+    int lx = f == 0, ly = f == 1, lz = f == 2;
+    rc |= field_alloc(m, m->Gn[f], lx, ly, lz);
+    rc |= field_alloc(m, m->Gm[f], lx, ly, lz);
+  }
+  if (rc) return OCN_ENOMEM;
+  default_bcs(m, m->u, false);
+  default_bcs(m, m->v, false);
+  default_bcs(m, m->w, false);
+  default_bcs(m, m->pNHS, true);
+  if (m->pHY.present) default_bcs(m, m->pHY, true);
+  for (int t = 0; t < m->nt; ++t) default_bcs(m, m->tr[t], false);
+  if (m->nu_e.present) {
+    default_bcs(m, m->nu_e, true);
+    for (int t = 0; t < m->nt; ++t)
+      if (m->kappa_e[t].present) default_bcs(m, m->kappa_e[t], true);
+  }
+  return OCN_OK;
+}
+
+// user boundary conditions of u, v, w, tracers, then -- closures with diffusivity fields only -- of nu_e and the kappa_e of every tracer
+// (boundary_conditions = (; kappa_e = (; b = ...)) of the reference: nonhydrostatic_model.jl:150-160, test_boundary_conditions_integration.jl:52-66)
+static int create_boundary_conditions(ocn_model* m, const ocn_model_desc* desc, bool smag) {
+  const ocn_grid* g = m->g;
+  const int nbc = 3 + m->nt + (smag ? 1 : desc->closure == OCN_CLOSURE_AMD ? 1 + m->nt : 0);
+  for (int f = 0; f < nbc; ++f) {
+    const int fd = f - (3 + m->nt);   // index among the diffusivity fields
+    Field* fld = f == 0 ? &m->u : f == 1 ? &m->v : f == 2 ? &m->w : f < 3 + m->nt ? &m->tr[f - 3] : fd == 0 ? &m->nu_e : &m->kappa_e[fd - 1];
+    for (int s = 0; s < 6; ++s) {
+      const ocn_bc& b = f < 3 + m->nt ? desc->bcs[f][s] : fd == 0 ? desc->nu_bcs[s] : desc->kappa_bcs[fd - 1][s];
+      if (b.kind == OCN_BC_DEFAULT) continue;
+      int dim = s / 2;
+      if (g->topo[dim] != OCN_BOUNDED) {
+        if (b.kind == OCN_BC_PERIODIC || b.kind == OCN_BC_NONE) continue;
+        ocn_set_error(m->ctx, "non-periodic boundary condition on a non-Bounded side (field %d side %d)", f, s);
+        return OCN_EINVAL;
+      }
+      BCdev bd{b.kind, b.value, nullptr};
+      if (b.array) {
+        // arrays span the two other directions' interior sizes (boundary_condition.jl getbc for arrays)
+        size_t nn = dim == 0 ? (size_t)g->N[1] * g->N[2] : dim == 1 ? (size_t)g->N[0] * g->N[2] : (size_t)g->N[0] * g->N[1];
+        double* dptr = nullptr;
+        if (hipMalloc((void**)&dptr, nn * sizeof(double)) != hipSuccess) return OCN_ENOMEM;
+        hipMemcpy(dptr, b.array, nn * sizeof(double), hipMemcpyHostToDevice);
+        m->owned.push_back(dptr);
+        bd.arr = dptr;
+      }
+      fld->bc[s] = bd;
+    }
+  }
+  // a quadratic drag is the Flux condition of its side: the halo fill treats it as one, k_drag_flux adds the flux to G^n
+  for (int f = 0; f < 2; ++f)
+    for (int sd = 0; sd < 2; ++sd)
+      if (m->tl.drag[f][sd].present) (f == 0 ? m->u : m->v).bc[OCN_BOTTOM + sd] = BCdev{OCN_BC_FLUX, 0.0, nullptr};
+  return OCN_OK;
+}
+
+// closure tables, scratch, and what the features read: their column tables and the background's field-form arrays
+static int create_feature_tables(ocn_model* m, const CreateArgs& a) {
+  const int Nz = m->g->N[2], nf = 3 + m->nt;
+  if (m->g->dist && hipMalloc((void**)&m->phi_below, (size_t)m->g->N[0] * m->g->N[1] * sizeof(double)) != hipSuccess) return OCN_ENOMEM;
+  if (m->d.closure == OCN_CLOSURE_AMD && amd_build_table(m) != OCN_OK) return OCN_ENOMEM;
+  if (a.smag)
+    if (int rc = smag_build_table(m)) return rc;
+  if (hipMalloc((void**)&m->d_red, 64) != hipSuccess) return OCN_ENOMEM;
+  m->stokes = (a.features & OCN_FEATURE_STOKES_DRIFT) != 0;
+  if (m->stokes && !m->stokes_tab.alloc(1, (size_t)6 * Nz)) return OCN_ENOMEM;
+  for (int f = 0; f < OCN_NF; ++f) m->force_ci[f] = m->bg_ci[f] = -1;
+  if (a.forcing) {
+    m->force_col = a.forcing->column_fields;
+    m->force_fld = a.forcing->field_fields;
+    int ncol = 0;
+    for (int f = 0; f < nf; ++f)   // u, v, w come as a block (internal.h force_col3): an undeclared one's tables stay zero
+      if ((m->force_col >> f & 1u) || (f < 3 && (m->force_col & 7u))) m->force_ci[f] = ncol++;
+    if (ncol && !m->force_tab.alloc(ncol, (size_t)3 * Nz)) return OCN_ENOMEM;
+  }
+  if (a.background) {
+    m->bg_col = a.background->column_members;
+    m->bg_fld = a.background->field_members;
+    int ncol = 0;
+    for (int f = 0; f < nf; ++f)
+      if (m->bg_col >> f & 1u) m->bg_ci[f] = ncol++;
+    // every parent level of the tallest field (w with a Bounded z)
+    if (ncol && !m->bg_tab.alloc(ncol, m->w.T[2] > m->u.T[2] ? m->w.T[2] : m->u.T[2])) return OCN_ENOMEM;
+    for (int f = 0; f < nf; ++f) {   // field form: allocated here, zero until set, so the addresses in a step graph hold
+      if (!(m->bg_fld >> f & 1u)) continue;
+      const size_t nb = bg_field_of(m, f).n * sizeof(double);
+      if (hipMalloc((void**)&m->bg_arr[f], nb) != hipSuccess || hipMemset(m->bg_arr[f], 0, nb) != hipSuccess) return OCN_ENOMEM;
+    }
+  }
+  return OCN_OK;
+}
+
+// which kernels serve the model, the predictor buffers of the tiled paths, the pressure solver
+static int create_paths_and_solver(ocn_model* m) {
+  fused_read_knobs(m);
+  m->fast_path = fused_available(m) ? 1 : 0;
+  m->bz_fast = (!m->fast_path && fused_bz_available(m)) ? 1 : 0;
+  if (getenv("OCNHIP_DEBUG")) {
+    char why[256];
+    fused_describe(m, why, sizeof(why));
+    fprintf(stderr, "[ocnhip] model: %s\n", why);
+  }
+  if (m->fast_path || m->bz_fast) {
+    int r2 = field_alloc(m, m->us, OCN_FACE, OCN_CENTER, OCN_CENTER) | field_alloc(m, m->vs, OCN_CENTER, OCN_FACE, OCN_CENTER) |
+             field_alloc(m, m->ws, OCN_CENTER, OCN_CENTER, OCN_FACE);
+    for (int t = 0; t < m->nt; ++t) r2 |= field_alloc(m, m->trs[t], OCN_CENTER, OCN_CENTER, OCN_CENTER);
+    if (r2) return OCN_ENOMEM;
+    for (int s = 0; s < 6; ++s) {   // the predictor is filled with the velocities' boundary conditions
+      m->us.bc[s] = m->u.bc[s];
+      m->vs.bc[s] = m->v.bc[s];
+      m->ws.bc[s] = m->w.bc[s];
+    }
+  }
+  m->solver = poisson_create(m);
+  return m->solver ? OCN_OK : OCN_EHIP;
+}
+
+// the body of all six creators
+static int model_create(ocn_grid* g, const ocn_model_desc* desc, CreateArgs a, ocn_model** out) {
+  if (!g || !desc || !out) return OCN_EINVAL;
+  // a descriptor that asks for nothing is an absent one
+  if (a.tilted && !a.tilted->has_gravity_vector && !a.tilted->coriolis_cartesian && !a.tilted->drag[0][0].present &&
+      !a.tilted->drag[0][1].present && !a.tilted->drag[1][0].present && !a.tilted->drag[1][1].present)
+    a.tilted = nullptr;
+  if (a.forcing && !(a.forcing->column_fields | a.forcing->field_fields)) a.forcing = nullptr;
+  if (a.background && !(a.background->column_members | a.background->field_members)) a.background = nullptr;
+  if (int rc = create_validate(g, desc, a)) return rc;
+  ocn_model* m = new ocn_model;
+  ModelGuard guard{m};
+  m->ctx = g->ctx;
+  m->d = *desc;
+  m->nt = desc->n_tracers;
+  if (int rc = create_inflate_halo(m, g)) return rc;
+  if (a.smag) {
+    // the molecular part of a (SmagorinskyLilly, ScalarDiffusivity) tuple stays in d.nu / d.kappa; alone: none
+    if (desc->closure == OCN_CLOSURE_NONE) {
+      m->d.nu = 0.0;
+      for (int t = 0; t < OCN_MAX_TRACERS; ++t) m->d.kappa[t] = 0.0;
+    }
+    m->d.closure = OCN_CLOSURE_SMAG;
+    m->smag_C = a.smag->C;
+    m->smag_Cb = a.smag->Cb;
+    for (int t = 0; t < m->nt; ++t) m->smag_rPr[t] = 1.0 / a.smag->Pr[t];
+  }
+  if (a.tilted) {
+    m->tl = *a.tilted;
+    m->tilt_terms = a.tilted->has_gravity_vector || a.tilted->coriolis_cartesian;
+    for (int f = 0; f < 2; ++f)
+      for (int sd = 0; sd < 2; ++sd) m->drag_any = m->drag_any || a.tilted->drag[f][sd].present;
+  }
+  m->gd = m->g->dev;
+  m->gd.nb = boundary_buffer[desc->advection];
+  if (int rc = create_fields(m, a.smag != nullptr)) return rc;
+  if (int rc = create_boundary_conditions(m, desc, a.smag != nullptr)) return rc;
+  if (int rc = create_feature_tables(m, a)) return rc;
+  if (int rc = create_paths_and_solver(m)) return rc;
+  update_state(m);  // nonhydrostatic_model.jl:200
+  m->ctx->models.push_back(m);
+  guard.m = nullptr;
+  *out = m;
+  return OCN_OK;
+}
+
+extern "C" {
+
+int ocn_model_create(ocn_grid* g, const ocn_model_desc* desc, ocn_model** out) { return model_create(g, desc, {}, out); }
+
+int ocn_model_create_smagorinsky_lilly(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, ocn_model** out) {
+  return smag ? model_create(g, desc, {smag}, out) : OCN_EINVAL;
+}
+
+int ocn_model_create_with(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features, ocn_model** out) {
+  return model_create(g, desc, {smag, features}, out);
+}
+
+int ocn_model_create_forced(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, ocn_model** out) {
+  return model_create(g, desc, {smag, features, forcing}, out);
+}
+
+int ocn_model_create_background(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                                const ocn_forcing_desc* forcing, const ocn_background_desc* background, ocn_model** out) {
+  return model_create(g, desc, {smag, features, forcing, background}, out);
+}
+
+int ocn_model_create_tilted(ocn_grid* g, const ocn_model_desc* desc, const ocn_smagorinsky_lilly_desc* smag, uint32_t features,
+                            const ocn_forcing_desc* forcing, const ocn_background_desc* background, const ocn_tilted_desc* tilted,
+                            ocn_model** out) {
+  return model_create(g, desc, {smag, features, forcing, background, tilted}, out);
+}
+
+// ---- the features' setters -------------------------------------------------------------------------------------------------
+static void host_scatter(const Field& f, const double* logical, const int lo[3], const int ext[3], std::vector<double>& phys);
+
+static int index_check(ocn_model* m, const char* who, const char* noun, int i) {
+  if (i < 0 || i >= 3 + m->nt) {
+    ocn_set_error(m->ctx, "%s: %s %d is outside 0..%d (u, v, w, then the model's tracers)", who, noun, i, 2 + m->nt);
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+static int stage_check(ocn_model* m, const char* who, int stage) {
+  if (stage < 0 || stage > 2) {
+    ocn_set_error(m->ctx, "%s: stage %d is outside 0..2", who, stage);
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+static int levels_check(ocn_model* m, const char* who, int n) {
+  if (n != m->gd.Nz) {
+    ocn_set_error(m->ctx, "%s: tables of %d entries on a grid of Nz = %d levels", who, n, m->gd.Nz);
+    return OCN_EINVAL;
+  }
+  return OCN_OK;
+}
+// field form: once no launch in flight reads the array being replaced, the box [lo, lo + ext) of f's parent layout lands in dev, zeros around it
+static int field_form_settle(ocn_model* m) {
+  if (halo_settle(m)) return OCN_EHIP;
+  OCN_HIP_CHECK(m->ctx, hipStreamSynchronize(m->ctx->stream));
+  return OCN_OK;
+}
+static int field_form_copy(ocn_model* m, const Field& f, const double* src, const int lo[3], const int ext[3], double* dev) {
+  std::vector<double> phys(f.n, 0.0);
+  host_scatter(f, src, lo, ext, phys);
+  OCN_HIP_CHECK(m->ctx, hipMemcpy(dev, phys.data(), f.n * sizeof(double), hipMemcpyHostToDevice));
+  return OCN_OK;
 }
 
 int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, const double* dz_vs_c, const double* dz_us_f,
@@ -1268,77 +1325,28 @@ int ocn_model_set_stokes_drift(ocn_model* m, int stage, const double* dz_us_c, c
     ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: the model was created without Stokes drift (ocn_model_create_with, OCN_FEATURE_STOKES_DRIFT)");
     return OCN_ESTATE;
   }
-  if (stage < 0 || stage > 2) {
-    ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: stage %d is outside 0..2", stage);
-    return OCN_EINVAL;
-  }
-  const int Nz = m->gd.Nz;
-  if (n != Nz) {
-    ocn_set_error(m->ctx, "ocn_model_set_stokes_drift: tables of %d entries on a grid of Nz = %d levels", n, Nz);
-    return OCN_EINVAL;
-  }
-  // library-owned staging: the caller's arrays are free again on return; a null table is the reference's addzero
-  const double* src[6] = {dz_us_c, dz_vs_c, dz_us_f, dz_vs_f, dt_us_c, dt_vs_c};
-  double* st = m->stokes_stage + (size_t)stage * 6 * Nz;
-  // the slot's previous upload may still be reading the staging memory: wait for that copy alone (it was queued ahead of the
-  // step that used it, so this does not wait for the stream to drain)
-  if (m->stokes_ev[stage]) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(m->stokes_ev[stage]));
-  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&m->stokes_ev[stage]));
-  for (int t = 0; t < 6; ++t) {
-    if (src[t]) memcpy(st + (size_t)t * Nz, src[t], (size_t)Nz * sizeof(double));
-    else memset(st + (size_t)t * Nz, 0, (size_t)Nz * sizeof(double));
-  }
-  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->stokes_dev + (size_t)stage * 6 * Nz, st, (size_t)6 * Nz * sizeof(double), hipMemcpyHostToDevice,
-                                       m->ctx->stream));
-  OCN_HIP_CHECK(m->ctx, hipEventRecord(m->stokes_ev[stage], m->ctx->stream));
-  return api_ret(m->ctx, OCN_OK);
-}
-
-static void host_scatter(const Field& f, const double* logical, const int lo[3], const int ext[3], std::vector<double>& phys);
-
-static int forcing_field_index(ocn_model* m, const char* who, int field) {
-  if (field < 0 || field >= 3 + m->nt) {
-    ocn_set_error(m->ctx, "%s: field %d is outside 0..%d (u, v, w, then the model's tracers)", who, field, 2 + m->nt);
-    return OCN_EINVAL;
-  }
-  return OCN_OK;
+  if (int rc = stage_check(m, "ocn_model_set_stokes_drift", stage)) return rc;
+  if (int rc = levels_check(m, "ocn_model_set_stokes_drift", n)) return rc;
+  const double* src[6] = {dz_us_c, dz_vs_c, dz_us_f, dz_vs_f, dt_us_c, dt_vs_c};   // a null table is the reference's addzero
+  return api_ret(m->ctx, m->stokes_tab.upload(m->ctx, stage, 0, src, 6, n));
 }
 
 int ocn_model_set_forcing_column(ocn_model* m, int field, int stage, const double* sigma, const double* tau, const double* F, int n) {
   if (!m) return OCN_EINVAL;
-  if (int rc = forcing_field_index(m, "ocn_model_set_forcing_column", field)) return rc;
+  if (int rc = index_check(m, "ocn_model_set_forcing_column", "field", field)) return rc;
   if (!(m->force_col >> field & 1u)) {
     ocn_set_error(m->ctx, "ocn_model_set_forcing_column: field %d was not declared in ocn_forcing_desc.column_fields at creation", field);
     return OCN_ESTATE;
   }
-  if (stage < 0 || stage > 2) {
-    ocn_set_error(m->ctx, "ocn_model_set_forcing_column: stage %d is outside 0..2", stage);
-    return OCN_EINVAL;
-  }
-  const int Nz = m->gd.Nz;
-  if (n != Nz) {
-    ocn_set_error(m->ctx, "ocn_model_set_forcing_column: tables of %d entries on a grid of Nz = %d levels", n, Nz);
-    return OCN_EINVAL;
-  }
-  // library-owned staging, as ocn_model_set_stokes_drift: wait for this (slot, field)'s previous copy alone, never for the stream
+  if (int rc = stage_check(m, "ocn_model_set_forcing_column", stage)) return rc;
+  if (int rc = levels_check(m, "ocn_model_set_forcing_column", n)) return rc;
   const double* src[3] = {sigma, tau, F};
-  const size_t at = ((size_t)stage * m->force_ncol + m->force_ci[field]) * 3 * Nz;
-  double* st = m->force_stage + at;
-  hipEvent_t& ev = m->force_ev[stage][field];
-  if (ev) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(ev));
-  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&ev));
-  for (int t = 0; t < 3; ++t) {
-    if (src[t]) memcpy(st + (size_t)t * Nz, src[t], (size_t)Nz * sizeof(double));
-    else memset(st + (size_t)t * Nz, 0, (size_t)Nz * sizeof(double));
-  }
-  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->force_dev + at, st, (size_t)3 * Nz * sizeof(double), hipMemcpyHostToDevice, m->ctx->stream));
-  OCN_HIP_CHECK(m->ctx, hipEventRecord(ev, m->ctx->stream));
-  return api_ret(m->ctx, OCN_OK);
+  return api_ret(m->ctx, m->force_tab.upload(m->ctx, stage, m->force_ci[field], src, 3, n));
 }
 
 int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, const double* tau, const double* F, int nx, int ny, int nz) {
   if (!m) return OCN_EINVAL;
-  if (int rc = forcing_field_index(m, "ocn_model_set_forcing_field", field)) return rc;
+  if (int rc = index_check(m, "ocn_model_set_forcing_field", "field", field)) return rc;
   if (!(m->force_fld >> field & 1u)) {
     ocn_set_error(m->ctx, "ocn_model_set_forcing_field: field %d was not declared in ocn_forcing_desc.field_fields at creation", field);
     return OCN_ESTATE;
@@ -1348,12 +1356,10 @@ int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, co
     ocn_set_error(m->ctx, "ocn_model_set_forcing_field: arrays of (%d, %d, %d) on a grid of (Nx, Ny, Nz) = (%d, %d, %d)", nx, ny, nz, N[0], N[1], N[2]);
     return OCN_EINVAL;
   }
-  if (halo_settle(m)) return OCN_EHIP;
-  OCN_HIP_CHECK(m->ctx, hipStreamSynchronize(m->ctx->stream));   // no launch in flight reads the arrays being replaced
+  if (int rc = field_form_settle(m)) return rc;
   const Field& f = *model_field(m, field < 3 ? field : OCN_F_TRACER + field - 3);   // the layout the kernels' offsets address
   const double* src[3] = {sigma, tau, F};
   const int lo[3] = {m->g->H[0], m->g->H[1], m->g->H[2]};
-  std::vector<double> phys;
   for (int t = 0; t < 3; ++t) {
     double*& dev = m->force_arr[field][t];
     if (!src[t]) {   // absent: the pointer is part of the step graphs' key, so graphs captured with the array are not replayed
@@ -1366,53 +1372,31 @@ int ocn_model_set_forcing_field(ocn_model* m, int field, const double* sigma, co
       ocn_set_error(m->ctx, "ocn_model_set_forcing_field: out of device memory");
       return OCN_ENOMEM;
     }
-    phys.assign(f.n, 0.0);
-    host_scatter(f, src[t], lo, N, phys);
-    OCN_HIP_CHECK(m->ctx, hipMemcpy(dev, phys.data(), f.n * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = field_form_copy(m, f, src[t], lo, N, dev)) return rc;
   }
   return api_ret(m->ctx, OCN_OK);
 }
 
-static int background_member_index(ocn_model* m, const char* who, int member) {
-  if (member < 0 || member >= 3 + m->nt) {
-    ocn_set_error(m->ctx, "%s: member %d is outside 0..%d (u, v, w, then the model's tracers)", who, member, 2 + m->nt);
-    return OCN_EINVAL;
-  }
-  return OCN_OK;
-}
-
 int ocn_model_set_background_column(ocn_model* m, int member, int stage, const double* table, int n) {
   if (!m) return OCN_EINVAL;
-  if (int rc = background_member_index(m, "ocn_model_set_background_column", member)) return rc;
+  if (int rc = index_check(m, "ocn_model_set_background_column", "member", member)) return rc;
   if (!(m->bg_col >> member & 1u)) {
     ocn_set_error(m->ctx, "ocn_model_set_background_column: member %d was not declared in ocn_background_desc.column_members at creation", member);
     return OCN_ESTATE;
   }
-  if (stage < 0 || stage > 2) {
-    ocn_set_error(m->ctx, "ocn_model_set_background_column: stage %d is outside 0..2", stage);
-    return OCN_EINVAL;
-  }
+  if (int rc = stage_check(m, "ocn_model_set_background_column", stage)) return rc;
   const int Tz = bg_field_of(m, member).T[2];
   if (n != Tz || !table) {
     ocn_set_error(m->ctx, "ocn_model_set_background_column: a table of %d entries for a field of %d parent levels (Nz + 2 Hz, + 1 for w with a Bounded z)",
                   table ? n : 0, Tz);
     return OCN_EINVAL;
   }
-  // library-owned staging, as ocn_model_set_stokes_drift: wait for this (slot, member)'s previous copy alone, never for the stream
-  const size_t at = ((size_t)stage * m->bg_ncol + m->bg_ci[member]) * m->bg_len;
-  double* st = m->bg_stage + at;
-  hipEvent_t& ev = m->bg_ev[stage][member];
-  if (ev) OCN_HIP_CHECK(m->ctx, hipEventSynchronize(ev));
-  else OCN_HIP_CHECK(m->ctx, hipEventCreate(&ev));
-  memcpy(st, table, (size_t)Tz * sizeof(double));
-  OCN_HIP_CHECK(m->ctx, hipMemcpyAsync(m->bg_dev + at, st, (size_t)Tz * sizeof(double), hipMemcpyHostToDevice, m->ctx->stream));
-  OCN_HIP_CHECK(m->ctx, hipEventRecord(ev, m->ctx->stream));
-  return api_ret(m->ctx, OCN_OK);
+  return api_ret(m->ctx, m->bg_tab.upload(m->ctx, stage, m->bg_ci[member], &table, 1, Tz));
 }
 
 int ocn_model_set_background_field(ocn_model* m, int member, const double* array, int tx, int ty, int tz) {
   if (!m) return OCN_EINVAL;
-  if (int rc = background_member_index(m, "ocn_model_set_background_field", member)) return rc;
+  if (int rc = index_check(m, "ocn_model_set_background_field", "member", member)) return rc;
   if (!(m->bg_fld >> member & 1u)) {
     ocn_set_error(m->ctx, "ocn_model_set_background_field: member %d was not declared in ocn_background_desc.field_members at creation", member);
     return OCN_ESTATE;
@@ -1423,12 +1407,9 @@ int ocn_model_set_background_field(ocn_model* m, int member, const double* array
                   array ? tz : 0, f.T[0], f.T[1], f.T[2]);
     return OCN_EINVAL;
   }
-  if (halo_settle(m)) return OCN_EHIP;
-  OCN_HIP_CHECK(m->ctx, hipStreamSynchronize(m->ctx->stream));   // no launch in flight reads the array being replaced
-  std::vector<double> phys(f.n, 0.0);
+  if (int rc = field_form_settle(m)) return rc;
   const int lo[3] = {0, 0, 0};
-  host_scatter(f, array, lo, f.T, phys);
-  OCN_HIP_CHECK(m->ctx, hipMemcpy(m->bg_arr[member], phys.data(), f.n * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = field_form_copy(m, f, array, lo, f.T, m->bg_arr[member])) return rc;
   return api_ret(m->ctx, OCN_OK);
 }
 
@@ -1480,23 +1461,11 @@ void ocn_model_destroy(ocn_model* m) {
   hipFree(m->phi_below);
   hipFree(m->amd_tab);
   hipFree(m->smag_tab);
-  hipFree(m->stokes_dev);
-  for (hipEvent_t e : m->stokes_ev)
-    if (e) hipEventDestroy(e);
-  free(m->stokes_stage);
-  hipFree(m->force_dev);
-  free(m->force_stage);
+  m->stokes_tab.release();
+  m->force_tab.release();
+  m->bg_tab.release();
   for (int f = 0; f < OCN_NF; ++f) {
-    for (int s = 0; s < 3; ++s) {
-      if (m->force_ev[s][f]) hipEventDestroy(m->force_ev[s][f]);
-      hipFree(m->force_arr[f][s]);
-    }
-  }
-  hipFree(m->bg_dev);
-  free(m->bg_stage);
-  for (int f = 0; f < OCN_NF; ++f) {
-    for (int s = 0; s < 3; ++s)
-      if (m->bg_ev[s][f]) hipEventDestroy(m->bg_ev[s][f]);
+    for (double* p : m->force_arr[f]) hipFree(p);
     hipFree(m->bg_arr[f]);
   }
   hipFree(m->ypack_s);

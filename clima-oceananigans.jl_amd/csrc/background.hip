@@ -248,7 +248,7 @@ __global__ void k_bg_c(GridDev g, BgVel b, BgTracers T, const double* __restrict
 static BgMem bg_member(const ocn_model* m, int f) {
   BgMem b = {nullptr, 0, 0, 0};
   if (m->bg_col >> f & 1u) {
-    b.p = m->bg_dev + ((size_t)(m->stage - 1) * m->bg_ncol + m->bg_ci[f]) * m->bg_len + m->gd.Hz;
+    b.p = m->bg_tab.slot(m->stage - 1, m->bg_ci[f]) + m->gd.Hz;
     b.sz = 1;
   } else if ((m->bg_fld >> f & 1u) && m->bg_arr[f]) {
     const Field& F = bg_field_of(m, f);

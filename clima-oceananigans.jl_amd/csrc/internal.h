@@ -97,6 +97,23 @@ struct Field {
 
 struct PoissonSolver;
 
+// Column tables of one feature: [3 stage slots][nitem][len] doubles on the device, library-owned host staging of the same shape
+// and one event per (slot, item), recorded behind that item's upload.  A setter copies the caller's runs into the staging memory
+// (the caller's arrays are free again on return) and queues one asynchronous copy on the context's stream; the next upload of
+// the same (slot, item) waits for that copy alone -- it was queued ahead of the step that used it, so this never waits for the
+// stream to drain.  The device addresses never change, so a captured step graph keeps reading the current contents.  (api.hip)
+struct StagedTables {
+  int nitem = 0;
+  size_t len = 0;
+  double *dev = nullptr, *stage = nullptr;
+  hipEvent_t ev[3][OCN_NF] = {};
+  bool alloc(int items, size_t length);   // zero-filled; false: out of memory
+  double* slot(int s, int item) const { return dev + ((size_t)s * nitem + item) * len; }
+  // nruns runs of runlen doubles, back to back from the start of the item; a null run is a run of zeros
+  int upload(ocn_ctx* ctx, int s, int item, const double* const* runs, int nruns, size_t runlen);
+  void release();
+};
+
 struct ocn_model {
   ocn_grid* g;
   ocn_ctx* ctx;
@@ -157,36 +174,25 @@ struct ocn_model {
   bool pnhs_deferred = false;
   bool pnhs_escaped = false;     // ocn_field_device_ptr(pNHS) was called: reads can no longer be seen, every projection stores
   int knob_eager_pressure = 0;   // OCNHIP_EAGER_PRESSURE=1: every projection stores pNHS (callers who read it after every step)
-  // UniformStokesDrift: the drift's four functions of (z, t) arrive as host tables (ocn_model_set_stokes_drift), one slot per
-  // stage.  Slot s holds six runs of Nz doubles: d_z u^s, d_z v^s at centres, the same at faces k = 1..Nz, d_t u^s, d_t v^s at
-  // centres.  The device addresses never change, so a captured step graph keeps reading the current contents.
+  // The features' functions of (z, t) arrive as host tables, one set per stage slot (StagedTables above).  UniformStokesDrift
+  // (ocn_model_set_stokes_drift): six runs of Nz doubles: d_z u^s, d_z v^s at centres, at faces k = 1..Nz, d_t u^s, d_t v^s at centres.
   int stokes = 0;                // created with Stokes drift (decides the path: never the all-in-one periodic one)
-  double* stokes_dev = nullptr;  // [3][6][Nz]
-  double* stokes_stage = nullptr;   // host staging of the same shape (the source of the asynchronous uploads)
-  hipEvent_t stokes_ev[3] = {nullptr, nullptr, nullptr};   // recorded behind each slot's upload
+  StagedTables stokes_tab;       // [3][1][6 Nz]
   // Forcing (ocn_model_create_forced): G_phi += sigma (tau - phi) + F for the fields of the two masks (bit f: u, v, w, tracers).
-  // Column form: force_dev holds, per stage slot and declared field (force_ci[f]: its rank among them), sigma, tau, F as three runs
-  // of Nz doubles; device addresses never change, so a captured step graph reads the current contents.  Field form: up to three
-  // arrays per field in the layout of that field's parent array (the tiled kernels read them at the cell's own byte offset, the
-  // general kernels at its interior index); an absent array is a null pointer and its load is skipped.  The pointers are part of
-  // the step graphs' key.
+  // Column form: per declared field (force_ci[f]: its rank among them) sigma, tau, F as three runs of Nz doubles.  Field form: up
+  // to three arrays per field in the layout of its parent array (the tiled kernels read them at the cell's own byte offset, the
+  // general kernels at its interior index); an absent one is null and its load skipped.  They are part of the step graphs' key.
   uint32_t force_col = 0, force_fld = 0;
-  int force_ncol = 0, force_ci[OCN_NF];
-  double* force_dev = nullptr;      // [3][force_ncol][3][Nz]
-  double* force_stage = nullptr;    // host staging of the same shape
-  hipEvent_t force_ev[3][OCN_NF] = {};   // recorded behind each (slot, field) upload
+  int force_ci[OCN_NF];
+  StagedTables force_tab;                // [3][declared fields][3 Nz]
   double* force_arr[OCN_NF][3] = {};     // field form: sigma, tau, F
   // BackgroundFields (ocn_model_create_background): G_phi -= div(adv, (U, V, W), phi) + div(adv, (u, v, w), Phi) with background
-  // velocities U, V, W (members 0, 1, 2) and background tracers (member 3 + t).  A member has one form.  Column form: bg_dev holds,
-  // per stage slot and declared member (bg_ci[f]: its rank among them), one table of bg_len doubles of which the first T[2] of
-  // the member's field are used -- every parent level, halo levels included; the device addresses never change, so a captured
-  // step graph reads the current contents.  Field form: one array in the layout of the parent array of the field it belongs to,
-  // allocated at creation (zero until set), so its address never changes either.
+  // velocities U, V, W (members 0, 1, 2) and background tracers (member 3 + t).  A member has one form.  Column form: per declared
+  // member (bg_ci[f]: its rank among them) one table as long as the tallest parent array; the first T[2] of the member's field are
+  // used, halo levels included.  Field form: one array in that field's parent layout, allocated at creation (zero until set).
   uint32_t bg_col = 0, bg_fld = 0;
-  int bg_ncol = 0, bg_ci[OCN_NF], bg_len = 0;
-  double* bg_dev = nullptr;        // [3][bg_ncol][bg_len]
-  double* bg_stage = nullptr;      // host staging of the same shape
-  hipEvent_t bg_ev[3][OCN_NF] = {};   // recorded behind each (slot, member) upload
+  int bg_ci[OCN_NF];
+  StagedTables bg_tab;             // [3][declared members][max T[2]]
   double* bg_arr[OCN_NF] = {};     // field form
   // Tilted gravity, ConstantCartesianCoriolis, quadratic drag (ocn_model_create_tilted): the descriptor as given.  tilt_terms: a
   // gravity vector or a Cartesian rotation is set, so the TILT instantiations of k_tend_uvw / k_rest4 (and, with a gravity vector,
@@ -204,22 +210,16 @@ inline Field& pred_w(ocn_model* m) { return m->pred_active ? m->ws : m->w; }
 inline bool pnhs_lazy(const ocn_model* m) { return m->fast_path && !m->g->dist && !m->knob_eager_pressure && !m->pnhs_escaped; }
 
 // the Stokes-drift tables a tendency launch reads: the slot of the current stage (null: no Stokes drift)
-inline const double* stokes_slot(const ocn_model* m) {
-  return m->stokes ? m->stokes_dev + (size_t)(m->stage - 1) * 6 * m->gd.Nz : nullptr;
-}
-
+inline const double* stokes_slot(const ocn_model* m) { return m->stokes ? m->stokes_tab.slot(m->stage - 1, 0) : nullptr; }
 // the column tables of u, v, w of the current stage, nine runs of Nz doubles (k_rest4): when one of the three is declared all three
 // have tables -- they are the first three of a slot -- and an undeclared one's stay zero.  Null: none of them is declared.
-inline const double* force_col3(const ocn_model* m) {
-  return (m->force_col & 7u) ? m->force_dev + (size_t)(m->stage - 1) * m->force_ncol * 3 * m->gd.Nz : nullptr;
-}
+inline const double* force_col3(const ocn_model* m) { return (m->force_col & 7u) ? m->force_tab.slot(m->stage - 1, 0) : nullptr; }
 inline bool model_forced(const ocn_model* m) { return (m->force_col | m->force_fld) != 0; }
 // what a tendency launch reads for field f (0, 1, 2: u, v, w; 3 + t: tracer t): the column tables of the current stage and the
 // field-form arrays, as parent bases (tiled kernels) or moved to the first interior cell (general kernels)
 inline ForceDev force_of(const ocn_model* m, int f, bool interior) {
   ForceDev fo = {nullptr, nullptr, nullptr, nullptr};
-  if (m->force_col >> f & 1u)
-    fo.col = m->force_dev + ((size_t)(m->stage - 1) * m->force_ncol + m->force_ci[f]) * 3 * m->gd.Nz;
+  if (m->force_col >> f & 1u) fo.col = m->force_tab.slot(m->stage - 1, m->force_ci[f]);
   if (m->force_fld >> f & 1u) {
     const Field& F = f == 0 ? m->u : f == 1 ? m->v : f == 2 ? m->w : m->tr[f - 3];
     const size_t org = interior ? (size_t)(F.interior() - F.d) : 0;
